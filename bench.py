@@ -33,7 +33,15 @@ cpu_baseline: CPU seconds (wait4 rusage) of reference runs taken when the proces
 (LDB; a bounded sample - the full-size pair would take the GPU run's time several times over); the one-frame figure at the benched geometry
 (the two live runs that differ by one coded frame) and the build container's full-size figure over the timed frames are reported beside it.
 
-  python bench.py --gpus N --steps K --warmup W [--streams S] [--width 3840 --height 2160] [--config ldb|ra|hdb16]
+Plain run and --full: a plain run sets up, warms up, times the K steps and prints the line - `value`, `ms_per_step` and the figures read from
+the encoder's own counters; it starts no reference process, compares nothing and leaves bit_exact null.  --full adds everything above that
+is not the headline figure: the verification (live and recorded reference runs), cpu_baseline and the measured host-to-device transfer
+(io.h2d).  --verify, --verify-frames, --cpu-sample, --no-verify and --no-cpu-baseline shape what --full does.
+--dump-outputs DIR (after the timed steps, rank 0's streams): what the timed path handed its caller in the last step - each stream's last
+coded frame (bitstream bytes) and a fixed, seeded sample of its reconstruction - as float32 / float64 .npy files, less than 64 MB in all
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--streams S] [--width 3840 --height 2160] [--config ldb|ra|hdb16]
                   [--bitdepth 8|10] [--sigma 2.0] [--verify auto|live|recorded] [--cpu-sample WxH] [--clip-frames F]
 For N > 1 launch with torch.distributed.run (one rank per GPU); streams are sharded across ranks with no data-path
 collective in the timed region ("weak" scaling: S streams per GPU); RCCL carries a consistency broadcast of the input
@@ -265,6 +273,39 @@ class CpuLegs:
         return open(os.path.join(self.dir.name, f'{tag}_{n}.{what}'), 'rb').read()
 
 
+DUMP_RECON_VALUES = 10 << 20   # --dump-outputs: reconstructed samples and their positions written (40 MiB) ...
+DUMP_BITS_VALUES = 4 << 20     # ... and bitstream bytes (float32, 16 MiB): with the small arrays, less than 64 MB in all
+
+
+def dump_outputs(out_dir, enc, bits, nframes, bitdepth):
+    """--dump-outputs: what the timed path handed its caller in its last step, one .npy file per array (S = streams of this rank):
+       recon_last_frame.npy      float32 [S, K]  each stream's last reconstructed frame at K fixed sample positions of the flat planar 4:2:0
+                                                 frame (a seeded sample, the same positions for every stream; every sample when they fit)
+       recon_sample_index.npy    float64 [K]     those positions
+       bits_last_frame.npy       float32 [B]     the bytes of each stream's last coded frame (4-byte size + payload), streams in order; at most
+                                                 DUMP_BITS_VALUES of them (the first ones)
+       bits_last_frame_bytes.npy float64 [S]     size of that frame per stream
+       bits_total_bytes.npy      float64 [S]     size of each stream's whole bitstream"""
+    os.makedirs(out_dir, exist_ok=True)
+    S = len(bits)
+    sample = np.dtype('<u2') if bitdepth > 8 else np.dtype(np.uint8)
+    fpx = enc.frame_bytes // sample.itemsize
+    k = min(fpx, max(1, DUMP_RECON_VALUES // (S + 2)))   # the float64 positions count as two values
+    idx = np.arange(fpx) if k == fpx else np.sort(np.random.default_rng(0).choice(fpx, k, replace=False))
+    rec = np.empty((S, k), dtype=np.float32)
+    for s in range(S):
+        rec[s] = enc.recon(s).view(sample)[idx]
+    last = []
+    for b in bits:
+        pre = stream_prefix(b, nframes - 1)
+        last.append(b[len(pre) if pre is not None else 0:])
+    blob = np.frombuffer(b''.join(last), dtype=np.uint8)[:DUMP_BITS_VALUES]
+    for name, arr in (('recon_last_frame', rec), ('recon_sample_index', idx.astype(np.float64)),
+                      ('bits_last_frame', blob.astype(np.float32)), ('bits_last_frame_bytes', np.array([len(x) for x in last], dtype=np.float64)),
+                      ('bits_total_bytes', np.array([len(b) for b in bits], dtype=np.float64))):
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+
+
 def est_run_s(nframes, w, h, S):
     """Rough wall time of the GPU run (input staging + frames), for sizing the CPU legs that should end with it."""
     return nframes * w * h * S / 90e6 + 30.0
@@ -394,7 +435,13 @@ def main():
                          'a shorter low-delay run is then a prefix of the recorded 25-frame reference runs and is verified against them')
     ap.add_argument('--cpu-sample', default=None, metavar='WxH',
                     help='with --verify recorded: geometry of the live CPU-baseline sample (top-left crop of stream 0, all frames); default: the benched geometry')
+    ap.add_argument('--full', action='store_true', help='also verify against the reference, measure cpu_baseline and io.h2d (a plain run times the steps only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (dump_outputs)')
     a = ap.parse_args()
+    if not a.full and (a.verify != 'auto' or a.verify_frames is not None or a.cpu_sample):
+        ap.error('--verify, --verify-frames and --cpu-sample shape a --full run')
+    verify_on = a.full and not a.no_verify        # reference comparisons (live legs, recorded runs)
+    base_on = a.full and not a.no_cpu_baseline    # cpu_baseline legs
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -484,7 +531,7 @@ def main():
     # Recorded reference runs (every rank, its own streams): {local stream index: record}.  A record of the same stream with more frames
     # serves a shorter low-delay run through its per-frame prefix hashes (the clip must have been generated for that length: --clip-frames).
     recorded, refs_note = {}, None
-    if a.verify in ('auto', 'recorded') and not a.no_verify:
+    if a.verify in ('auto', 'recorded') and verify_on:
         refs = load_bench_refs(cfg_path)
         refs_note = refs.pop('_note', None)
         for s_ in range(S):
@@ -495,7 +542,7 @@ def main():
             missing = [my_ids[s_] for s_ in sorted({0, S // 2, S - 1}) if s_ not in recorded]
             if missing:
                 raise KeyError(f'--verify recorded: no recorded reference run for streams {missing} of this workload (scripts/record_bench_refs.py)')
-    live = a.verify in ('auto', 'live') and not a.no_verify and rank == 0 and legs.available() and (cw, ch) == (w, h)
+    live = a.verify in ('auto', 'live') and verify_on and rank == 0 and legs.available() and (cw, ch) == (w, h)
     # N > 1 (round 6): rank 0 starts NO reference process beside the timed region of a weak-scaling figure when recorded reference runs verify the
     # run anyway (every rank checks its own recorded streams); live legs remain the fall-back for workloads nobody recorded.  cpu_baseline: N = 1 only.
     if world > 1 and live and recorded and a.verify == 'auto':
@@ -503,8 +550,8 @@ def main():
     if a.verify == 'recorded':
         nv = nframes
     verify = {}        # local stream index -> [host frames or None, {coded frame: (display index, md5 of the GPU reconstruction)}]
-    do_verify = not a.no_verify and (live or bool(recorded))
-    do_base = rank == 0 and world == 1 and not a.no_cpu_baseline and legs.available()
+    do_verify = verify_on and (live or bool(recorded))
+    do_base = rank == 0 and world == 1 and base_on and legs.available()
     n_ref = nframes if reordered else nv   # with frame reordering the coding order depends on the chunk length: run it all
     vs_live = sorted({0, S // 2, S - 1}) if live else []
     for s_ in recorded:
@@ -647,7 +694,7 @@ def main():
     # timed with events: `io.h2d.value_including_h2d` adds that time to every step as if nothing overlapped it (a double-buffered upload would hide it
     # behind the seconds a step takes).
     h2d = None
-    if have_gpu and rank == 0:
+    if have_gpu and rank == 0 and a.full:
         try:
             nb = min(S, 32)
             hbuf = torch.empty(nb * fpx * bps, dtype=torch.uint8).pin_memory()
@@ -682,6 +729,8 @@ def main():
         if rank == 0:
             assert len(allbits) == S * world and allbits[:S] == local_bits, 'ordered gather lost the chunk order'
     t_g = time.perf_counter() - t_g
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, enc, local_bits, nframes, a.bitdepth)
     stats = enc.stats() if hasattr(enc, 'stats') else None
     kinfo = None
     if have_gpu:   # registers / LDS / workgroups per CU of the superblock kernel as the runtime reports them (an occupancy regression shows in the line)
@@ -701,7 +750,9 @@ def main():
     rc = 0
     if rank == 0:
         res = {'bit_exact': None, 'checked': [], 'cpu_baseline': None}
-        if not legs.available():
+        if not a.full:
+            res['note'] = 'bit-exactness is not checked in a plain run: bench.py --full compares with the reference'
+        elif not legs.available():
             res['note'] = 'oracle/_ref/Thorenc not in the snapshot: bit-exactness not checked in this run'
         elif a.no_verify:
             res['note'] = 'verification disabled (--no-verify)'
@@ -711,7 +762,7 @@ def main():
         if do_base:
             try:
                 res['cpu_baseline'] = cpu_baseline_object(times, base_tag, tf_legs, nv, n_ref, reordered, a, p, w, h, cw, ch, legs, world, my_ids,
-                                                          load_bench_refs(cfg_path) if not a.no_verify else {}, qp, clipn)
+                                                          load_bench_refs(cfg_path) if verify_on else {}, qp, clipn)
             except (RuntimeError, KeyError) as e:
                 print(f'bench.py: {e}', file=sys.stderr)
                 res['cpu_baseline'] = {'value': None, 'unit': 'Mpixels/s', 'cores': 1, 'kind': 'reference', 'sample': None, 'error': str(e)}

@@ -2,7 +2,7 @@
 """Record what the reference encoder (oracle/_ref/Thorenc) produces for streams of bench.py's workload: bitstream md5 + size and the
 md5 of every reconstructed frame (display order) -> tests/golden/bench_refs.json.  For the operating points whose reference runs are
 too long to wait for on the GPU box (3840x2160 RA: ~5 min, 3840x2160 10-bit HDB16 with its 17-frame chunk: ~11 min per stream on one
-core): `bench.py --verify recorded` compares the GPU's streams with these records instead of live runs.  Build container only
+core): `bench.py --full --verify recorded` compares the GPU's streams with these records instead of live runs.  Build container only
 (`make -C oracle` first); the clips come from the seeded generator, exactly as bench.py builds them.
   python scripts/record_bench_refs.py --config ra --frames 9 --streams 96 [--width 3840 --height 2160 --bitdepth 8 --sigma 2 -j 3]"""
 import argparse, hashlib, json, os, subprocess, sys, tempfile

@@ -60,7 +60,8 @@ def test_bench_prints_one_contract_line(monkeypatch):
     import thor_amd
     import bench
     monkeypatch.setattr(thor_amd, 'Encoder', _FakeEncoder)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--streams', '3', '--width', '64', '--height', '64', '--steps', '2', '--warmup', '1', '--no-verify'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--streams', '3', '--width', '64', '--height', '64', '--steps', '2', '--warmup', '1', '--no-verify',
+                                      '--full'])
     monkeypatch.delenv('WORLD_SIZE', raising=False)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
@@ -89,6 +90,46 @@ def test_bench_prints_one_contract_line(monkeypatch):
         assert c['cores'] == 1 and c['kind'] == 'reference' and c['unit'] == d['unit']
 
 
+class _DumpFakeEncoder(_FakeEncoder):
+    def recon(self, stream):
+        import numpy as np
+        return np.full(self.frame_bytes, 7 + stream, dtype=np.uint8)
+
+    def bitstream(self, stream):   # three framed frames (4-byte size + payload); the last one of stream s has s + 1 payload bytes
+        return b''.join(len(p).to_bytes(4, 'big') + p for p in (b'ab', b'c', b'\x05' * (stream + 1)))
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_last_step(monkeypatch, tmp_path):
+    """Without --full no reference process starts, nothing is compared and io.h2d is not measured; --dump-outputs writes the last timed
+    step's outputs (each stream's last coded frame and its reconstruction) as float32 / float64 arrays."""
+    import numpy as np
+    import thor_amd
+    import bench
+    monkeypatch.setattr(thor_amd, 'Encoder', _DumpFakeEncoder)
+    monkeypatch.setattr(bench.CpuLegs, 'start', lambda *a, **k: pytest.fail('a plain run started a reference process'))
+    monkeypatch.delenv('WORLD_SIZE', raising=False)
+    argv = ['bench.py', '--streams', '3', '--width', '64', '--height', '64', '--steps', '2', '--warmup', '1']
+    monkeypatch.setattr(sys, 'argv', argv + ['--dump-outputs', str(tmp_path / 'out')])
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main()
+    lines = [l for l in buf.getvalue().splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] >= 0 and d['roofline']['launches'] == 2
+    assert d['bit_exact'] is None and 'cpu_baseline' not in d and d['io']['h2d'] is None and '--full' in d['bit_exact_note']
+    out = {f[:-4]: np.load(tmp_path / 'out' / f) for f in os.listdir(tmp_path / 'out')}
+    assert sorted(out) == ['bits_last_frame', 'bits_last_frame_bytes', 'bits_total_bytes', 'recon_last_frame', 'recon_sample_index']
+    assert all(x.dtype in (np.float32, np.float64) for x in out.values())
+    assert out['recon_last_frame'].shape == (3, 64 * 64 * 3 // 2) and (out['recon_last_frame'] == np.array([[7], [8], [9]])).all()
+    assert (out['recon_sample_index'] == np.arange(64 * 64 * 3 // 2)).all()
+    assert out['bits_last_frame_bytes'].tolist() == [5, 6, 7] and out['bits_total_bytes'].tolist() == [16, 17, 18]
+    assert out['bits_last_frame'].tolist() == [0, 0, 0, 1, 5, 0, 0, 0, 2, 5, 5, 0, 0, 0, 3, 5, 5, 5]
+    monkeypatch.setattr(sys, 'argv', argv + ['--verify', 'live'])   # the verification options shape a --full run
+    with pytest.raises(SystemExit):
+        bench.main()
+
+
 class _SlowFakeEncoder(_FakeEncoder):
     """Every lock-step frame takes a while: the reference legs of a small geometry finish long BEFORE the timed region ends
     (the situation of the driver's 25-frame run, where round 3's poll-time stamps produced 73 Mpixels/s)."""
@@ -103,7 +144,8 @@ def test_cpu_baseline_is_a_single_core_rate_when_the_legs_finish_early(monkeypat
     import thor_amd
     import bench
     monkeypatch.setattr(thor_amd, 'Encoder', _SlowFakeEncoder)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--streams', '2', '--width', '320', '--height', '192', '--steps', '3', '--warmup', '4', '--no-verify'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--streams', '2', '--width', '320', '--height', '192', '--steps', '3', '--warmup', '4', '--no-verify',
+                                      '--full'])
     monkeypatch.delenv('WORLD_SIZE', raising=False)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
@@ -146,7 +188,8 @@ def test_cpu_baseline_with_frame_reordering_subtracts_the_intra_frame(monkeypatc
     import thor_amd
     import bench
     monkeypatch.setattr(thor_amd, 'Encoder', _ReorderFakeEncoder)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'ra', '--streams', '2', '--width', '192', '--height', '128', '--steps', '8', '--warmup', '1', '--no-verify'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'ra', '--streams', '2', '--width', '192', '--height', '128', '--steps', '8', '--warmup', '1', '--no-verify',
+                                      '--full'])
     monkeypatch.delenv('WORLD_SIZE', raising=False)
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
@@ -179,7 +222,7 @@ def test_recorded_verification_rejects_a_wrong_stream(monkeypatch, tmp_path):
         assert all(bench.ref_key('ldb', 192, 128, 8, 32, 3, 2.0, s) in rec for s in (0, 1, 2))
         monkeypatch.setattr(thor_amd, 'Encoder', _ReconFakeEncoder)
         monkeypatch.setattr(sys, 'argv', ['bench.py', '--streams', '3', '--width', '192', '--height', '128', '--steps', '2', '--warmup', '1', '--verify', 'recorded',
-                                          '--cpu-sample', '128x64'])
+                                          '--cpu-sample', '128x64', '--full'])
         monkeypatch.delenv('WORLD_SIZE', raising=False)
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf), pytest.raises(SystemExit) as ex:
@@ -290,7 +333,7 @@ def test_verification_passes_on_bit_exact_streams_live_and_recorded(monkeypatch)
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     monkeypatch.setattr(thor_amd, 'Encoder', _HostsimEncoder)
     monkeypatch.delenv('WORLD_SIZE', raising=False)
-    base = ['bench.py', '--streams', '3', '--width', '192', '--height', '128', '--steps', '2', '--warmup', '1']
+    base = ['bench.py', '--streams', '3', '--width', '192', '--height', '128', '--steps', '2', '--warmup', '1', '--full']
 
     def run(extra):
         monkeypatch.setattr(sys, 'argv', base + extra)
