@@ -133,6 +133,33 @@ void thor_hip_kernel_time_reset(thor_hip_encoder* e);
  * shortcut (any block size), out[1] superblocks early-skipped as a whole, out[2] superblocks processed, out[3] luma
  * pixels processed.  reset != 0 clears the counters. */
 void thor_hip_read_stats(thor_hip_encoder* e, unsigned long long out[4], int reset);
+/* Per-frame log and the encoder report (enc/mainenc.c:219-226, :553-591, :642-666).  Every coded frame of a stream appends one record
+ * (thor_hip_begin_sequence empties the log).  With frame distortion on, one more kernel per frame group sums (original - final
+ * reconstruction)^2 per plane on the device - after deblocking, CDEF and CLPF - and the sums travel with the frame's bit counts; off (the
+ * default) a frame's launches and copies are unchanged and sse / psnr stay 0 (the reference's -snrcalc 0). */
+void thor_hip_set_frame_distortion(thor_hip_encoder* e, int on);
+typedef struct thor_hip_frame_stats {
+  int display_index;          /* absolute input frame index, as the reference prints it (the -skip 3 chunk starts at 3) */
+  int frame_type;             /* 0 = I, 1 = P, 2 = B */
+  int qp;
+  int num_bits;               /* bits of the frame before the 4-byte framing; the sequence header is not counted */
+  int num_ref;
+  int ref_array[4];           /* window indices as coded; -1 = the interpolated frame, built from the next two entries */
+  int ref_frame_num[4];       /* chunk-relative frame number of the frame each ref_array entry points at (-1 for the -1 entry) */
+  int has_sse;                /* 1 when the frame's distortion was measured */
+  unsigned long long sse[3];  /* Y, U, V: exact sums of squared differences */
+  double psnr[3];             /* snr_yuv's formula on sse (common/snr.c:32-99); inf when sse == 0; 0 when not measured */
+} thor_hip_frame_stats;
+int thor_hip_frame_stats_count(const thor_hip_encoder* e, int stream);
+/* Record i (coding order) of a stream.  Returns 0, 1 on a bad argument. */
+int thor_hip_get_frame_stats(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_stats* out);
+/* The reference's stdout for the stream so far, byte for byte ("SH:" line, one line per coded frame, average block), written to buf like
+ * snprintf: at most n bytes including the terminating NUL; returns the length of the whole report. */
+int thor_hip_report(const thor_hip_encoder* e, int stream, char* buf, size_t n);
+/* The line the reference appends to its -stat file for the stream so far (without the header " NFR     kbps     PSNRY  PSNRU  PSNRV"
+ * that starts a new file); num_frames: the -n value.  snprintf semantics as above. */
+int thor_hip_stat_line(const thor_hip_encoder* e, int stream, int num_frames, char* buf, size_t n);
+
 /* Development aid: 32 shader-cycle / event counters summed over all superblock wavefronts (all zero unless
  * the library was built with -DTHOR_PROF). */
 void thor_hip_read_prof(thor_hip_encoder* e, long long out[32]);
@@ -208,6 +235,10 @@ int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int width, int h
 /* interpolate_frames(new, ref0, ref1, 2, 1) (common/temporal_interp.c:909: the frame half way between two reference pictures; luma pyramid,
  * block motion estimation per level, merge, motion-compensated average) through the engine's own device path (tk_interp_dev.h). */
 int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv);
+
+/* Per-plane sums of squared differences between two planar 4:2:0 frames a and b (w x h; bitdepth 8: bytes, 9..12: uint16_t) through the
+ * encoder's own kernel (k_frame_sse): out[0] Y, out[1] U, out[2] V, exact.  w, h: multiples of 8.  Returns 0, 1 = bad argument, 3 = no device. */
+int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth, unsigned long long out[3]);
 
 /* Resources of the persistent superblock kernel (sample_bytes 1: 8-bit kernel, 2: 16-bit kernel, 0: the 8-bit kernel's second build for runs of few
  * streams - 256 registers, two workgroups per CU, chosen by the library when a run cannot fill more; THOR_HIP_KERNEL=std|lat|wide forces one; 3: its third build - eight wavefronts per workgroup, one workgroup per CU, for runs of very few streams) as the HIP runtime reports them: registers per lane,

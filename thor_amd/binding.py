@@ -60,6 +60,13 @@ class ThorParams(C.Structure):
 FRAMES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)   # thor_hip_frames_done_fn
 
 
+class FrameStats(C.Structure):
+    """thor_hip_frame_stats (include/thor_hip.h): one coded frame of a stream's log."""
+    _fields_ = [('display_index', C.c_int), ('frame_type', C.c_int), ('qp', C.c_int), ('num_bits', C.c_int), ('num_ref', C.c_int),
+                ('ref_array', C.c_int * 4), ('ref_frame_num', C.c_int * 4), ('has_sse', C.c_int), ('sse', C.c_ulonglong * 3),
+                ('psnr', C.c_double * 3)]
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -89,6 +96,12 @@ def lib():
         L.thor_hip_read_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
         L.thor_hip_deblock_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_deblock_frame_hbd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_set_frame_distortion.argtypes = [C.c_void_p, C.c_int]
+        L.thor_hip_frame_stats_count.argtypes = [C.c_void_p, C.c_int]
+        L.thor_hip_get_frame_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameStats)]
+        L.thor_hip_report.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+        L.thor_hip_stat_line.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+        L.thor_hip_frame_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         _LIB = L
@@ -238,6 +251,31 @@ class Encoder:
         px, sb = max(int(a[3]), 1), max(int(a[2]), 1)
         return {'early_skip_pixel_fraction': round(int(a[0]) / px, 4), 'early_skip_sb128_fraction': round(int(a[1]) / sb, 4),
                 'inter_superblocks': int(a[2]), 'inter_luma_pixels': int(a[3])}
+
+    def set_frame_distortion(self, on=True):
+        """Measure the per-plane SSE of every coded frame on the GPU (thor_hip_set_frame_distortion; off by default)."""
+        lib().thor_hip_set_frame_distortion(self.h, 1 if on else 0)
+
+    def frame_stats(self, stream):
+        """The stream's log of coded frames in coding order (thor_hip_get_frame_stats): a list of dicts."""
+        L, out, f = lib(), [], FrameStats()
+        for i in range(L.thor_hip_frame_stats_count(self.h, stream)):
+            if L.thor_hip_get_frame_stats(self.h, stream, i, C.byref(f)):
+                raise RuntimeError('thor_hip_get_frame_stats failed')
+            nr = f.num_ref
+            out.append({'display_index': f.display_index, 'type': 'IPB'[f.frame_type], 'qp': f.qp, 'num_bits': f.num_bits,
+                        'ref_array': list(f.ref_array)[:nr], 'ref_frame_num': list(f.ref_frame_num)[:nr], 'has_sse': bool(f.has_sse),
+                        'sse': [int(v) for v in f.sse], 'psnr': [float(v) for v in f.psnr]})
+        return out
+
+    def report(self, stream):
+        """The reference encoder's stdout report for the stream so far (thor_hip_report)."""
+        n = lib().thor_hip_report(self.h, stream, None, 0)
+        if n < 0:
+            raise ValueError('bad stream')
+        buf = C.create_string_buffer(n + 1)
+        lib().thor_hip_report(self.h, stream, buf, n + 1)
+        return buf.value.decode()
 
     def __enter__(self):
         return self
@@ -393,3 +431,16 @@ def kat_interpolate(yuv0, yuv1, width, height, bitdepth=8):
     out = np.zeros_like(a)
     _kat('thor_hip_kat_interpolate', _vp(a), _vp(b), width, height, bitdepth, _vp(out))
     return out
+
+
+def frame_sse(a, b, width, height, bitdepth=8):
+    """Per-plane (Y, U, V) sums of squared differences of two planar 4:2:0 frames on the GPU (thor_hip_frame_sse, kernel k_frame_sse)."""
+    T = _pix(bitdepth)
+    a = np.ascontiguousarray(a, dtype=T).reshape(-1); b = np.ascontiguousarray(b, dtype=T).reshape(-1)
+    if a.size != width * height * 3 // 2 or b.size != a.size:
+        raise ValueError('frame size does not match width x height 4:2:0')
+    out = (C.c_ulonglong * 3)()
+    rc = lib().thor_hip_frame_sse(_vp(a), _vp(b), width, height, bitdepth, out)
+    if rc:
+        raise RuntimeError(f'thor_hip_frame_sse returned {rc}')
+    return [int(v) for v in out]

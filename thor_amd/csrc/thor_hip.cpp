@@ -69,6 +69,20 @@ template <typename PIX> __global__ void k_make_ref(const RefJob<PIX>* rj) {
   make_ref_rows(R.rec, R.ref, R.width, R.height, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, (int)blockDim.x);
 }
 
+// Per-plane SSE of the final reconstruction against the original (frame_sse_rows), streams along y: each wavefront takes rows
+// (blockIdx.x * 4 + wave, + 4 * gridDim.x, ...), sums its lanes' 64-bit partials with DPP and adds them to the stream's slots with one
+// 64-bit atomic per plane.  Integer sums: the result does not depend on the order.
+template <typename PIX> __global__ __launch_bounds__(256) void k_frame_sse(const FrameJob<PIX>* jobs, unsigned long long* out) {
+  const FrameJob<PIX>& J = jobs[blockIdx.y];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  unsigned long long acc[3] = {0, 0, 0};
+  frame_sse_rows(J.orig, J.rec, J.cfg.width, J.cfg.height, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64, acc);
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long v = wave_sum64_dpp(acc[k]);
+    if (lane == 0 && v) atomicAdd(&out[4 * (size_t)blockIdx.y + k], v);
+  }
+}
+
 // Bit-level concatenation: one workgroup per item.  dst is zero-filled; words are OR-ed in.
 __global__ void k_gather_bits(const backend::GatherItem* items, int n, uint32_t* dst) {
   const int it = blockIdx.x;
@@ -530,6 +544,18 @@ template void run_deblock<uint16_t>(const FrameJob<uint16_t>*, const FrameJob<ui
 template void run_make_ref<uint16_t>(const FrameJob<uint16_t>*, const Plane3<uint16_t>*, int);
 template void run_cdef<uint16_t>(const CdefJob<uint16_t>*, const CdefJob<uint16_t>*, int);
 }  // namespace backend
+
+// jobs: device array of S FrameJob (orig, rec, geometry); out: device, 4 slots per stream, cleared by the caller on g_stream.
+// Up to 64 four-wavefront workgroups per stream (2 * height rows: Y, U, V).
+template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const FrameJob<PIX>* hjobs, int S, unsigned long long* out) {
+  if (S <= 0) return;
+  const int rows = 2 * hjobs[0].cfg.height;
+  const int blocks = (rows + 3) / 4 < 64 ? (rows + 3) / 4 : 64;
+  hipLaunchKernelGGL(k_frame_sse<PIX>, dim3(blocks, S), dim3(256), 0, g_stream, jobs, out);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_frame_sse<uint8_t>(const FrameJob<uint8_t>*, const FrameJob<uint8_t>*, int, unsigned long long*);
+template void launch_frame_sse<uint16_t>(const FrameJob<uint16_t>*, const FrameJob<uint16_t>*, int, unsigned long long*);
 }  // namespace tk
 
 // ---------------------------------------------------------------------------------------------
@@ -839,6 +865,46 @@ void thor_hip_kernel_time_reset(thor_hip_encoder*) { g_clk.sb_ms = g_clk.filt_ms
 void thor_hip_read_stats(thor_hip_encoder* e, unsigned long long out[4], int reset) {
   if (!e || !out) return;
   ENC_DISPATCH(e, { backend::d2h(out, E.eng.d_stats, 4 * sizeof(unsigned long long)); if (reset) backend::dev_memset(E.eng.d_stats, 0, 8 * sizeof(unsigned long long)); });
+}
+
+void thor_hip_set_frame_distortion(thor_hip_encoder* e, int on) {
+  if (!e) return;
+  ENC_DISPATCH(e, { E.eng.frame_distortion = on != 0; });
+}
+static const std::vector<FrameStat>* stream_log(const thor_hip_encoder* e, int stream) {
+  if (!e || stream < 0 || stream >= e->S) return nullptr;
+  return e->hbd ? &e->e16->eng.st[stream].log : &e->e8->eng.st[stream].log;
+}
+static int stream_sh_bits(const thor_hip_encoder* e, int stream) { return e->hbd ? e->e16->eng.st[stream].sh_bits : e->e8->eng.st[stream].sh_bits; }
+static int copy_out(const std::string& r, char* buf, size_t n) {
+  if (buf && n) { const size_t k = r.size() < n - 1 ? r.size() : n - 1; memcpy(buf, r.data(), k); buf[k] = 0; }
+  return (int)r.size();
+}
+int thor_hip_frame_stats_count(const thor_hip_encoder* e, int stream) {
+  const std::vector<FrameStat>* log = stream_log(e, stream);
+  return log ? (int)log->size() : 0;
+}
+int thor_hip_get_frame_stats(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_stats* out) {
+  const std::vector<FrameStat>* log = stream_log(e, stream);
+  if (!log || !out || i < 0 || i >= (int)log->size()) return 1;
+  const FrameStat& f = (*log)[i];
+  memset(out, 0, sizeof(*out));
+  out->display_index = f.display; out->frame_type = f.frame_type; out->qp = f.qp; out->num_bits = f.num_bits; out->num_ref = f.num_ref;
+  for (int k = 0; k < 4; k++) { out->ref_array[k] = f.ref_array[k]; out->ref_frame_num[k] = f.ref_array[k] < 0 ? -1 : f.ref_frame_num[k]; }
+  out->has_sse = f.has_sse;
+  for (int k = 0; k < 3; k++) out->sse[k] = f.sse[k];
+  frame_psnr(f, e->sp.width, e->sp.height, e->sp.bitdepth, out->psnr);
+  return 0;
+}
+int thor_hip_report(const thor_hip_encoder* e, int stream, char* buf, size_t n) {
+  const std::vector<FrameStat>* log = stream_log(e, stream);
+  if (!log) return -1;
+  return copy_out(format_report(*log, stream_sh_bits(e, stream), e->sp.max_num_ref, e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.bitdepth), buf, n);
+}
+int thor_hip_stat_line(const thor_hip_encoder* e, int stream, int num_frames, char* buf, size_t n) {
+  const std::vector<FrameStat>* log = stream_log(e, stream);
+  if (!log) return -1;
+  return copy_out(format_stat_line(*log, stream_sh_bits(e, stream), e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.bitdepth, num_frames), buf, n);
 }
 
 }  // extern "C"
@@ -1459,6 +1525,29 @@ extern "C" int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int w
                                  const int* strength, int fb_log2, const uint8_t* fb_on, uint32_t* stats, void* out_yuv) {
   KAT_BD(kat_clpf<uint8_t>((const uint8_t*)rec_yuv, (const uint8_t*)org_yuv, width, height, 8, qp, cells, strength, fb_log2, fb_on, stats, (uint8_t*)out_yuv),
          kat_clpf<uint16_t>((const uint16_t*)rec_yuv, (const uint16_t*)org_yuv, width, height, bitdepth, qp, cells, strength, fb_log2, fb_on, stats, (uint16_t*)out_yuv));
+}
+// Per-plane SSE of two host frames through k_frame_sse (the kernel the engine launches with frame distortion on).
+template <typename PIX> int frame_sse_host(const PIX* a, const PIX* b, int width, int height, unsigned long long out[3]) {
+  if (!a || !b || !out || width % 8 || height % 8 || width < 8 || height < 8) return 1;
+  if (!ensure_init(g_inited ? g_device : 0)) return 3;
+  DevFrame<PIX> fa, fb;
+  fa.alloc(width, height, 0); fb.alloc(width, height, 0);
+  kat_upload(fa, a, width, height); kat_upload(fb, b, width, height);
+  FrameJob<PIX> J;
+  memset(&J, 0, sizeof(J));
+  J.cfg.width = width; J.cfg.height = height; J.orig = fa.p; J.rec = fb.p;
+  FrameJob<PIX>* dj = (FrameJob<PIX>*)backend::dev_alloc(sizeof(J));
+  unsigned long long* dout = (unsigned long long*)backend::dev_alloc(4 * sizeof(unsigned long long));  // zeroed
+  backend::h2d(dj, &J, sizeof(J));
+  launch_frame_sse<PIX>(dj, &J, 1, dout);
+  backend::dev_sync();
+  backend::d2h(out, dout, 3 * sizeof(unsigned long long));
+  backend::dev_free(dj); backend::dev_free(dout); fa.release(); fb.release();
+  return 0;
+}
+extern "C" int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth, unsigned long long out[3]) {
+  KAT_BD(frame_sse_host<uint8_t>((const uint8_t*)a, (const uint8_t*)b, w, h, out),
+         frame_sse_host<uint16_t>((const uint16_t*)a, (const uint16_t*)b, w, h, out));
 }
 extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
   KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),

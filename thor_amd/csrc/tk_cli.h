@@ -17,6 +17,8 @@ struct CliArgs {
   SeqParams sp;
   std::string infile, outfile, recfile;
   int num_frames = 600, skip = 0, streams = 1;
+  int snrcalc = 1;           // -snrcalc (enc/strings.c:340): PSNR of every frame in the report
+  std::string statfile;      // -stat FILE: one summary line per stream appended (enc/mainenc.c:652-667)
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -51,6 +53,8 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
     else if (k == "-n") a.num_frames = I();
     else if (k == "-skip") a.skip = I();
     else if (k == "-streams") a.streams = I();
+    else if (k == "-snrcalc") a.snrcalc = I();
+    else if (k == "-stat") a.statfile = v;
     else if (k == "-width") p.width = I();
     else if (k == "-height") p.height = I();
     else if (k == "-qp") p.qp = I();
@@ -99,7 +103,7 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
     else {
       // the rest of the reference's table: harmless at their defaults (or never read by the block path), fatal otherwise
       struct Opt { const char* name; const char* dflt; };  // dflt == nullptr: any value is fine (I/O and reporting options)
-      static const Opt rest[] = {{"-ph", "0"}, {"-fh", "0"}, {"-stat", nullptr}, {"-snrcalc", nullptr}, {"-log2_sb_size", "7"},
+      static const Opt rest[] = {{"-ph", "0"}, {"-fh", "0"}, {"-log2_sb_size", "7"},
                                  {"-max_delta_qp", "0"}, {"-delta_qp_step", nullptr}, {"-sync", "0"}, {"-bitrate", "0"},
                                  {"-max_qp", nullptr}, {"-min_qp", nullptr}, {"-max_qpI", nullptr}, {"-min_qpI", nullptr},
                                  {"-qmtx", "0"}, {"-qmtx_offset", nullptr}, {"-subsample", "420"}, {"-frame_bitdepth", nullptr}};
@@ -135,12 +139,14 @@ static inline CliArgs cli_parse(int argc, char** argv) {
 // Encode `num_frames` frames of a raw 4:2:0 file with S identical-geometry streams: stream s
 // codes frames [skip + s*num_frames, skip + (s+1)*num_frames) as its own closed stream (what the
 // reference produces with -skip/-n).  Outputs "<of>" for S==1, "<of>.<s>" otherwise.
+// stdout: the reference's report (tk_report.h); with S > 1 every stream's, in stream order, each after a line "stream <s>".
 template <typename PIX> int cli_run(const CliArgs& a) {
   const SeqParams& p = a.sp;
   FILE* fi = fopen(a.infile.c_str(), "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", a.infile.c_str()); return 2; }
   const size_t fsz = (size_t)p.width * p.height * 3 / 2;
   Engine<PIX> eng;
+  eng.frame_distortion = a.snrcalc != 0;
   eng.open(p, a.streams);
   std::vector<PIX> frame(fsz), rec(fsz);
   std::vector<FILE*> fr(a.streams, nullptr);
@@ -220,6 +226,13 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       fclose(fo);
     }
   }
+  for (int s = 0; s < a.streams; s++) {
+    if (a.streams > 1) printf("stream %d\n", s);
+    fputs(format_report(eng.st[s].log, eng.st[s].sh_bits, p.max_num_ref, p.frame_rate, p.width, p.height, p.bitdepth).c_str(), stdout);
+    if (!a.statfile.empty())
+      append_stat_file(a.statfile.c_str(), format_stat_line(eng.st[s].log, eng.st[s].sh_bits, p.frame_rate, p.width, p.height, p.bitdepth, a.num_frames));
+  }
+  fflush(stdout);
   eng.close();
   fclose(fi);
   return 0;

@@ -18,6 +18,8 @@
 #include "tk_cdef.h"
 #include "tk_interp_dev.h"
 #include "tk_clpf.h"
+#include "tk_filters.h"
+#include "tk_report.h"
 
 namespace tk {
 
@@ -48,6 +50,11 @@ void release_superblocks(const void* jobs);
 // motion compensation, padding); jobs/hjobs: device/host arrays of n idev::Job
 template <typename PIX> void run_interp(const idev::Job<PIX>* jobs, const idev::Job<PIX>* hjobs, int n);  // frees the scheduler state run_superblocks keeps for this job array
 }  // namespace backend
+#if !TK_HOST
+// Per-plane sums of squared differences orig - rec of S streams into out[4 * s + plane] (added: the caller clears the slots), one launch
+// (thor_hip.cpp: k_frame_sse).  The host build calls frame_sse_rows directly (Engine::finish_frames).
+template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const FrameJob<PIX>* hjobs, int S, unsigned long long* out);
+#endif
 
 // ---- parameters -------------------------------------------------------------------------
 struct SeqParams {  // the enc_params fields this path honours (enc/mainenc.h:35-112)
@@ -346,6 +353,8 @@ template <typename PIX> struct Stream {
   HostBits bits;             // bits of the frame being assembled (sequence header rides on frame 0)
   int bit_phase = 0;         // raw_frames mode: bit position mod 32 of the caller's stream at frame start
   std::vector<uint8_t> out;  // finished stream bytes (4-byte big-endian length + payload per frame)
+  int sh_bits = 0;           // bits of the sequence header
+  std::vector<FrameStat> log;  // one record per coded frame, in coding order (cleared by begin_sequence)
 };
 
 // The caller-visible fields of the reference's deblock_data_t (common/types.h:178-187) in declaration order, from one DbCell:
@@ -383,6 +392,8 @@ template <typename PIX> class Engine {
   long long* d_prof = nullptr;  // 32 cycle counters summed over all superblocks (THOR_PROF builds)
   idev::Job<PIX>* d_ijobs = nullptr;
   std::vector<idev::Job<PIX>> h_ijobs;
+  bool frame_distortion = false;        // measure the per-plane SSE of every coded frame (off: a frame's launches and copies are unchanged)
+  unsigned long long* d_sse = nullptr;  // [S][4]: Y, U, V sums of the frame just finished (allocated on first use)
 
   void open(const SeqParams& p, int num_streams) {
     sp = p; S = num_streams;
@@ -447,6 +458,7 @@ template <typename PIX> class Engine {
         s.clpf_fb_on = (uint8_t*)backend::dev_alloc((size_t)((p.width + 31) / 32) * ((p.height + 31) / 32));
       }
       if (!raw_frames) write_sequence_header(s.bits, sp);
+      s.sh_bits = s.bits.nbits;
     }
     d_ljobs = (ClpfJob<PIX>*)backend::dev_alloc(sizeof(ClpfJob<PIX>) * S);
     h_ljobs.resize(S);
@@ -483,6 +495,7 @@ template <typename PIX> class Engine {
     backend::dev_free(d_prof); d_prof = nullptr;
     backend::dev_free(d_stats); d_stats = nullptr;
     backend::dev_free(d_ijobs); d_ijobs = nullptr;
+    backend::dev_free(d_sse); d_sse = nullptr;
   }
 
   // planar 4:2:0 frame in host memory -> device `orig` of stream s
@@ -536,7 +549,7 @@ template <typename PIX> class Engine {
 
   // Coding-order schedule.  begin_sequence fixes the chunk [skip, skip+num_frames) of an input holding
   // file_frames frames (needed for the reference's end-of-sequence behaviour with reordered GOPs).
-  void begin_sequence(int s, int skip, int num_frames, int file_frames) { st[s].gop.init(sp, skip, num_frames, file_frames); }
+  void begin_sequence(int s, int skip, int num_frames, int file_frames) { st[s].gop.init(sp, skip, num_frames, file_frames); st[s].log.clear(); }
   // Next frame to code for stream s: fills st[s].cur / st[s].cur_abs; false when the chunk is finished.
   bool schedule(int s) {
     Stream<PIX>& q = st[s];
@@ -739,6 +752,20 @@ template <typename PIX> class Engine {
       } else
         for (int s = first; s < end; s++) lplan[s] = clpf_plan(nullptr, sp.width, sp.height, fp[s].qp, h_jobs[s].lambda, sp.max_clpf_strength);
     }
+    // the frame's record (mainenc.c:553-591); the frame numbers of its references are read before the window moves
+    for (int s = first; s < end; s++) {
+      Stream<PIX>& q = st[s];
+      const FrameParams& f = fp[s];
+      FrameStat r;
+      r.display = f.frame_num + (q.gop.started ? q.gop.skip : 0);
+      r.frame_type = f.frame_type; r.qp = f.qp; r.num_ref = f.num_ref;
+      for (int k = 0; k < kMaxRefs; k++) {
+        r.ref_array[k] = f.ref_array[k];
+        r.ref_frame_num[k] = f.ref_array[k] >= 0 && f.ref_array[k] < ring_size ? q.ring[f.ref_array[k]].frame_num : -1;
+      }
+      r.num_bits = -q.bits.nbits;  // completed below, when the frame's bits are assembled
+      q.log.push_back(r);
+    }
     // sliding window: the slot shifted out becomes ref[0] (encode_frame.c:826-835)
     std::vector<Plane3<PIX>> dst(S);
     for (int s = first; s < end; s++) {
@@ -750,7 +777,25 @@ template <typename PIX> class Engine {
       dst[s] = q.ring[0].p;
     }
     backend::run_make_ref<PIX>(h_jobs.data() + first, dst.data() + first, count);
+    if (frame_distortion) {  // per-plane SSE of the final reconstructions (after deblocking, CDEF, CLPF)
+      if (!d_sse) d_sse = (unsigned long long*)backend::dev_alloc((size_t)S * 4 * sizeof(unsigned long long));
+      backend::dev_memset(d_sse + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long));
+#if TK_HOST
+      for (int s = first; s < end; s++) frame_sse_rows(h_jobs[s].orig, h_jobs[s].rec, sp.width, sp.height, 0, 1, 0, 1, d_sse + (size_t)s * 4);
+#else
+      launch_frame_sse<PIX>(d_jobs + first, h_jobs.data() + first, count, d_sse + (size_t)first * 4);
+#endif
+    }
     backend::dev_sync();
+    if (frame_distortion) {
+      std::vector<unsigned long long> sse((size_t)count * 4);
+      backend::d2h(sse.data(), d_sse + (size_t)first * 4, sse.size() * sizeof(unsigned long long));
+      for (int s = first; s < end; s++) {
+        FrameStat& r = st[s].log.back();
+        r.has_sse = 1;
+        for (int k = 0; k < 3; k++) r.sse[k] = sse[(size_t)(s - first) * 4 + k];
+      }
+    }
     // bitstream assembly: one D2H of all bit counts, a device-side bit-level gather of the per-SB
     // strings into one compact buffer, one D2H of that buffer.
     // (arrays indexed by stream: only the entries of [first, end) are filled and used)
@@ -819,6 +864,7 @@ template <typename PIX> class Engine {
       }
       if (sp.clpf)
         for (auto& pr : lplan[s].bits) b.put(pr.first, pr.second);
+      q.log.back().num_bits += b.nbits;
       q.num_encoded++;
       if (q.gop.started) q.gop.advance(f);
       if (raw_frames) continue;

@@ -127,4 +127,43 @@ TK_DEV void make_ref_rows(const Plane3<PIX>& rec, const Plane3<PIX>& ref, int wi
   }
 }
 
+// Sum of squared differences between the original and the final reconstruction, per plane (the sums snr_yuv, common/snr.c:32-99,
+// turns into PSNR; bitdepth == input_bitdepth, so no shifts).  One work item per row (Y rows, then U, then V) like make_ref_rows;
+// `lane`/`nlanes` stride along the row in vectors of 16 bytes, the tail (chroma widths are multiples of 4, not of 16 bytes) in
+// vectors of 4 samples.  Rows must start 16-byte aligned (DevFrame strides are multiples of 16 samples).  Adds into acc[plane]:
+// exact 64-bit sums (at 12 bits one square is up to 4095^2, a 32-bit sum of a row would overflow after 257 samples).
+template <typename PIX>
+TK_DEV void frame_sse_rows(const Plane3<PIX>& org, const Plane3<PIX>& rec, int width, int height, int gid, int gsize, int lane, int nlanes,
+                           unsigned long long acc[3]) {
+  constexpr int kV = 16 / (int)sizeof(PIX);
+  struct alignas(16) V16 { PIX v[kV]; };
+  struct alignas(4 * sizeof(PIX)) V4 { PIX v[4]; };
+  const int total = height + height;  // Y rows + U rows + V rows
+  for (int it = gid; it < total; it += gsize) {
+    const PIX* a;
+    const PIX* b;
+    int w, pl;
+    if (it < height) { a = org.y + (size_t)it * org.sy; b = rec.y + (size_t)it * rec.sy; w = width; pl = 0; }
+    else if (it < height + height / 2) { const int r = it - height; a = org.u + (size_t)r * org.sc; b = rec.u + (size_t)r * rec.sc; w = width / 2; pl = 1; }
+    else { const int r = it - height - height / 2; a = org.v + (size_t)r * org.sc; b = rec.v + (size_t)r * rec.sc; w = width / 2; pl = 2; }
+    const int nv = w / kV;
+    unsigned long long s = 0;
+    for (int i = lane; i < nv; i += nlanes) {
+      const V16 va = ((const V16*)a)[i], vb = ((const V16*)b)[i];
+      unsigned int q = 0;  // at most 8 squares of 4095^2 < 2^28
+      for (int k = 0; k < kV; k++) { const int d = (int)va.v[k] - (int)vb.v[k]; q += (unsigned int)(d * d); }
+      s += q;
+    }
+    for (int i = nv * (kV / 4) + lane; i < w / 4; i += nlanes) {
+      const V4 va = ((const V4*)a)[i], vb = ((const V4*)b)[i];
+      unsigned int q = 0;
+      for (int k = 0; k < 4; k++) { const int d = (int)va.v[k] - (int)vb.v[k]; q += (unsigned int)(d * d); }
+      s += q;
+    }
+    acc[0] += pl == 0 ? s : 0;  // constant indices: acc stays in registers on the device
+    acc[1] += pl == 1 ? s : 0;
+    acc[2] += pl == 2 ? s : 0;
+  }
+}
+
 }  // namespace tk

@@ -1,9 +1,12 @@
 /* thorenc_hip.c - minimal C front end over the libthor_hip.so sequence API (include/thor_hip.h).
  * Usage mirrors the reference Thorenc (enc/strings.c:287-356) for the options this path honours:
  *   thorenc_hip -cf config.txt -if in.yuv -width W -height H -qp Q -n N [-skip K] [-f fps]
- *               [-of str.bit] [-rf rec.yuv] [-streams S] [-name value ...]
+ *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-name value ...]
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
+ * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
+ * S > 1 every stream's, in stream order, each after a line "stream <s>" - then the throughput line.  -stat appends the reference's
+ * summary line of every stream to the file.
  * All input frames are staged in HBM first; the timed region covers the encode loop only. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,7 +23,8 @@ static double now_s(void) {
 int main(int argc, char** argv) {
   thor_hip_params p;
   const char *inf = NULL, *of = NULL, *rf = NULL;
-  int n = 600, skip = 0, S = 1, i, wrap = 0;
+  const char* statf = NULL;
+  int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
   for (i = 1; i + 1 < argc; i += 2)
@@ -34,6 +38,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-n")) n = atoi(v);
     else if (!strcmp(k, "-skip")) skip = atoi(v);
     else if (!strcmp(k, "-streams")) S = atoi(v);
+    else if (!strcmp(k, "-snrcalc")) snrcalc = atoi(v);
+    else if (!strcmp(k, "-stat")) statf = v;
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -44,6 +50,7 @@ int main(int argc, char** argv) {
   unsigned char* frame = (unsigned char*)malloc(fsz);
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
+  thor_hip_set_frame_distortion(e, snrcalc != 0);
   for (int s = 0; s < S; s++)
     for (int f = 0; f < n; f++) {
       size_t idx = (size_t)skip + (size_t)s * n + f;
@@ -86,6 +93,26 @@ int main(int argc, char** argv) {
     if (fr[s])
       for (int f = 0; f < n; f++)
         if (recs[(size_t)s * n + f]) fwrite(recs[(size_t)s * n + f], 1, fsz, fr[s]);
+  for (int s = 0; s < S; s++) {
+    int len = thor_hip_report(e, s, NULL, 0);
+    char* rep = (char*)malloc((size_t)len + 1);
+    thor_hip_report(e, s, rep, (size_t)len + 1);
+    if (S > 1) fprintf(stdout, "stream %d\n", s);
+    fputs(rep, stdout);
+    free(rep);
+    if (statf) {
+      char line[256];
+      FILE* sf = fopen(statf, "r");
+      int not_exists = !sf;
+      if (sf) fclose(sf);
+      thor_hip_stat_line(e, s, n, line, sizeof line);
+      if ((sf = fopen(statf, "a")) != NULL) {
+        if (not_exists) fputs(" NFR     kbps     PSNRY  PSNRU  PSNRV\n", sf);
+        fputs(line, sf);
+        fclose(sf);
+      }
+    }
+  }
   n = coded;
   double sb_ms = 0, filt_ms = 0; long launches = 0;
   thor_hip_kernel_time(e, &sb_ms, &launches, &filt_ms);
