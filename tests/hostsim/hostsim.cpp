@@ -2,7 +2,7 @@
 // Compiles the engine headers with -DTHOR_HOSTSIM (1-lane teams, plain loops) into a CPU
 // executable so that the bit-exactness of the algorithm can be checked against the reference
 // encoder (oracle/_ref/Thorenc) in a container without a GPU.  The product library
-// (thor_amd/csrc/thor_hip.cpp) never links or calls this; it has no CPU path.
+// (thor_amd/csrc/thor_hip.cpp and its hip_*.h parts) never links or calls this; it has no CPU path.
 //
 // With -DTHOR_HOSTSIM_LANES=N (N a power of two <= 64, e.g. 8) every superblock is processed by a team of N lanes, each lane
 // an OS thread executing the same SPMD code as a GPU lane; barriers, ballots, shuffles and reductions go through one
@@ -291,20 +291,8 @@ template <typename PIX> void run_interp(const idev::Job<PIX>* jobs, const idev::
     }
   }
 }
-template void run_interp<uint8_t>(const idev::Job<uint8_t>*, const idev::Job<uint8_t>*, int);
-template void run_interp<uint16_t>(const idev::Job<uint16_t>*, const idev::Job<uint16_t>*, int);
-template void run_clpf_stats<uint8_t>(const ClpfJob<uint8_t>*, const ClpfJob<uint8_t>*, int);
-template void run_clpf_stats<uint16_t>(const ClpfJob<uint16_t>*, const ClpfJob<uint16_t>*, int);
-template void run_clpf_apply<uint8_t>(const ClpfJob<uint8_t>*, const ClpfJob<uint8_t>*, int);
-template void run_clpf_apply<uint16_t>(const ClpfJob<uint16_t>*, const ClpfJob<uint16_t>*, int);
-template void run_cdef<uint8_t>(const CdefJob<uint8_t>*, const CdefJob<uint8_t>*, int);
-template void run_cdef<uint16_t>(const CdefJob<uint16_t>*, const CdefJob<uint16_t>*, int);
-template void run_superblocks<uint8_t>(const FrameJob<uint8_t>*, const FrameJob<uint8_t>*, int, const SbRange*);
-template void run_superblocks<uint16_t>(const FrameJob<uint16_t>*, const FrameJob<uint16_t>*, int, const SbRange*);
-template void run_deblock<uint8_t>(const FrameJob<uint8_t>*, const FrameJob<uint8_t>*, int);
-template void run_deblock<uint16_t>(const FrameJob<uint16_t>*, const FrameJob<uint16_t>*, int);
-template void run_make_ref<uint8_t>(const FrameJob<uint8_t>*, const Plane3<uint8_t>*, int);
-template void run_make_ref<uint16_t>(const FrameJob<uint16_t>*, const Plane3<uint16_t>*, int);
+TK_BACKEND_INSTANTIATE(uint8_t)
+TK_BACKEND_INSTANTIATE(uint16_t)
 }  // namespace backend
 }  // namespace tk
 

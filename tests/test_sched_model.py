@@ -1,4 +1,4 @@
-"""Model check of the superblock dependency scheduler (thor_amd/csrc/tk_sched.h:df_finish, used by thor_hip.cpp:k_superblocks).
+"""Model check of the superblock dependency scheduler (thor_amd/csrc/tk_sched.h:df_finish, used by tk_kernel.h:k_superblocks).
 
 The kernel releases a task when its dependency counter reaches `need`; a finishing task (k,l) bumps the counters
 of  (k,l+1),  (k+1,l-1)  and, in the last column,  (k+1,l).  This test restates that successor rule and checks,

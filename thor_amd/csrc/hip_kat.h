@@ -1,0 +1,458 @@
+// hip_kat.h - C ABI, kernel-level batch entry points for the known-answer tests ("KAT"), and thor_hip_superblock_kernel_info / _in_use (part of the
+// translation unit thor_hip.cpp: the kernels here run the very device functions the superblock kernel calls).
+#pragma once
+namespace tk {
+// The kernels behind the known-answer entry points run the product's device code on one block / transform unit per workgroup of
+// one wavefront; PIX = uint8_t (the reference's _lbd functions) or uint16_t (_hbd, bitdepth 9..12).
+template <typename PIX>
+__global__ __launch_bounds__(64) void k_kat_sad(const PIX* org, int w, int h, const PIX* refp, int rstride, int bx, int by, const int* cand, int n,
+                                               uint32_t* out) {
+  // the product's full-pel evaluator (tk_me.h:seg_sads, row segment per lane), plane reads only (no search window)
+  const Team t = mk_team((int)threadIdx.x, 64);
+  struct KC { const PIX* p; int dx, dy; };
+  MeWin win;
+  win.on = 0; win.w32 = nullptr; win.ox = win.oy = win.Ww = win.Wh = win.pitch = 0;
+  auto cnd = [&](int c) -> KC {
+    KC x;
+    x.dx = cand[2 * c]; x.dy = cand[2 * c + 1];
+    x.p = refp + (size_t)(by + x.dy) * rstride + bx + x.dx;
+    return x;
+  };
+  seg_sads<SP_GLOBAL>(t, n, org, w, rstride, w, h, win, cnd, [&](int c, const KC&, int sad, int mine) { if (mine) out[c] = (uint32_t)sad; });
+}
+template <typename PIX>
+__global__ __launch_bounds__(64) void k_kat_interp(const PIX* ref0, int rstride, int pic_w, int pic_h, int bx, int by, int w, int h,
+                                                  const int16_t* mv, int bipred, int bitdepth, PIX* out) {
+  const Team t = mk_team((int)threadIdx.x, 64);
+  const int i = blockIdx.x;
+  pred_luma<SP_GLOBAL>(t, out + (size_t)i * w * h, w, ref0 + (size_t)by * rstride + bx, rstride, w, h, mk_mv(mv[2 * i], mv[2 * i + 1]), 0,
+            bipred, pic_w, pic_h, bx, by, bitdepth);
+}
+template <typename PIX>
+__global__ __launch_bounds__(64) void k_kat_tu(const PIX* org, const PIX* pred, int size, int qp, int coeff_type, int fast, int bitdepth,
+                                              int16_t* coefq, PIX* rec, int* cbp) {
+  __shared__ XformWs xf;
+  __shared__ XformTabs tabs;
+  __shared__ int16_t cq[256];
+  const Team t = mk_team((int)threadIdx.x, 64, tabs.izz);
+  xf.prof = nullptr;
+  xf.tabs = &tabs;
+  xform_tables_fill(&tabs, (int)threadIdx.x, 64);
+  t.sync();
+  const int i = blockIdx.x, qs = size < 16 ? size : 16;
+  const size_t o = (size_t)i * size * size;
+  int c = code_tu(t, &xf, org + o, size, pred + o, size, rec + o, size, size, qp, coeff_type, fast, cq, bitdepth);
+  for (int k = threadIdx.x; k < qs * qs; k += 64) coefq[(size_t)i * qs * qs + k] = cq[k];
+  if (threadIdx.x == 0) cbp[i] = c;
+}
+
+// ---- round 6: known-answer kernels for the sample kernels that were only covered by whole-stream hashes -------------------------
+// One wavefront per item, running exactly the device functions the encoder calls.
+template <typename PIX>
+__global__ __launch_bounds__(64) void k_kat_intra(const PIX* plane, int stride, int bitdepth, int size, int tb_split, const int* par, const PIX* rblocks,
+                                                 PIX* out) {
+  __shared__ IntraEdge<PIX> edge;
+  const Team t = mk_team((int)threadIdx.x, 64);
+  const int it = blockIdx.x;
+  const int* q = par + 7 * it;   // ypos, xpos (coding block), upright, downleft, mode, i, j (transform unit inside the block)
+  const int cbs = tb_split ? 2 * size : size;
+  const PIX* rblock = tb_split ? rblocks + (size_t)it * cbs * cbs + q[5] * cbs + q[6] : nullptr;
+  make_edges<SP_GLOBAL>(t, &edge, plane + (size_t)q[0] * stride + q[1], stride, rblock, cbs, q[5], q[6], q[0], q[1], size, q[2], q[3], tb_split, bitdepth);
+  pred_intra<SP_GLOBAL>(t, &edge, q[0] + q[5], q[1] + q[6], size, out + (size_t)it * size * size, size, q[4], bitdepth);
+}
+// (pred_inter_yuv / improve_uv are __noinline__ functions the superblock kernel calls too: a kernel with a larger register budget calling them would raise
+// THEIR budget and with it the superblock kernel's VGPR count - 227 instead of 168, two workgroups per CU instead of three, measured in round 6 - so these two
+// kernels carry the superblock kernel's launch bounds)
+template <typename PIX>
+__global__ __launch_bounds__(kWgThreads, (sizeof(PIX) == 1 ? (int)kOcc : 2)) void k_kat_inter_yuv(Plane3<PIX> ref, int width, int height, int bitdepth, int size, const int* par, const int16_t* mv, PIX* out) {
+  const Team t = mk_team((int)threadIdx.x, 64);
+  const int it = blockIdx.x;
+  const int* q = par + 5 * it;   // ypos, xpos, sign, enable_bipred, split
+  mv_t m[4];
+  for (int k = 0; k < 4; k++) m[k] = mk_mv(mv[(it * 4 + k) * 2], mv[(it * 4 + k) * 2 + 1]);
+  PIX* o = out + (size_t)it * (size * size * 3 / 2);
+  pred_inter_yuv<SP_GLOBAL>(t, ref, o, o + size * size, o + size * size * 5 / 4, q[0], q[1], size, size, size, m, q[2], width, height, q[3], q[4], bitdepth);
+}
+template <typename PIX> __global__ __launch_bounds__(64) void k_kat_average(const PIX* a, const PIX* b, int size, PIX* out) {
+  const Team t = mk_team((int)threadIdx.x, 64);
+  const size_t o = (size_t)blockIdx.x * (size * size * 3 / 2);
+  const int n = size * size, c = n / 4;
+  average_yuv<SP_GLOBAL>(t, out + o, out + o + n, out + o + n + c, a + o, a + o + n, a + o + n + c, b + o, b + o + n, b + o + n + c, size, size, size);
+}
+template <typename PIX>
+__global__ __launch_bounds__(kWgThreads, (sizeof(PIX) == 1 ? (int)kOcc : 2)) void k_kat_cfl(const PIX* y, PIX* uv, const PIX* ry, int n, int bitdepth) {
+  const Team t = mk_team((int)threadIdx.x, 64);
+  const int it = blockIdx.x, c = (n / 2) * (n / 2);
+  improve_uv<PIX, SP_GLOBAL>(t, nullptr, y + (size_t)it * n * n, uv + (size_t)it * 2 * c, uv + (size_t)it * 2 * c + c, ry + (size_t)it * n * n, n, n, n, bitdepth);
+}
+template <typename PIX> __global__ void k_kat_cdef_dir(const PIX* blocks, int n, int cs, int* dir, int* var) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  int v = 0;
+  dir[i] = cdef_find_dir(blocks + (size_t)i * 64, 8, &v, cs);
+  var[i] = v;
+}
+template <typename PIX>
+__global__ __launch_bounds__(64) void k_kat_cdef_filter(const PIX* plane, int w, int h, int stride, int bsize, int cs, const int* par, PIX* out) {
+  const int it = blockIdx.x, k = threadIdx.x;
+  if (k >= bsize * bsize) return;
+  const int* q = par + 7 * it;   // x0, y0, pri, sec, dir, pri_damping, sec_damping
+  const int x = q[0] + k % bsize, y = q[1] + k / bsize;
+  out[(size_t)it * bsize * bsize + k] = (PIX)cdef_filter_px(plane, stride, x, y, w, h, q[2], q[3], q[4], q[5], q[6], cs);
+}
+}  // namespace tk
+
+template <typename PIX>
+static int kat_sad_batch(const PIX* org, int w, int h, const PIX* ref_plane, int plane_w, int plane_h, int rstride, int bx, int by, const int* cand,
+                         int n, uint32_t* out) {
+  if (!org || !ref_plane || !cand || !out || n <= 0 || w < 4 || h < 4 || (w & (w - 1)) || (h & (h - 1))) return 1;
+  for (int i = 0; i < n; i++) {
+    int x = bx + cand[2 * i], y = by + cand[2 * i + 1];
+    if (x < 0 || y < 0 || x + w > plane_w || y + h > plane_h) return 2;
+  }
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_org((size_t)w * h, org);
+  // the evaluator reads whole 16-byte row segments: 16 zeroed samples of slack behind the plane on the device (dev_alloc clears);
+  // only the caller's rstride * plane_h samples are read from the host buffer
+  DevBuf<PIX> d_ref((size_t)rstride * plane_h + 16);
+  backend::h2d(d_ref, ref_plane, (size_t)rstride * plane_h * sizeof(PIX));
+  DevBuf<int> d_c((size_t)2 * n, cand);
+  DevBuf<uint32_t> d_o(n);
+  hipLaunchKernelGGL(k_kat_sad<PIX>, dim3(1), dim3(64), 0, g_stream, d_org, w, h, d_ref, rstride, bx, by, d_c, n, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, (size_t)n * 4);
+  return 0;
+}
+extern "C" int thor_hip_sad_batch(const uint8_t* org, int w, int h, const uint8_t* ref_plane, int plane_w, int plane_h, int rstride,
+                                  int bx, int by, const int* cand, int n, uint32_t* out) {
+  return kat_sad_batch<uint8_t>(org, w, h, ref_plane, plane_w, plane_h, rstride, bx, by, cand, n, out);
+}
+extern "C" int thor_hip_sad_batch_hbd(const uint16_t* org, int w, int h, const uint16_t* ref_plane, int plane_w, int plane_h, int rstride,
+                                      int bx, int by, const int* cand, int n, uint32_t* out) {
+  return kat_sad_batch<uint16_t>(org, w, h, ref_plane, plane_w, plane_h, rstride, bx, by, cand, n, out);
+}
+
+template <typename PIX>
+static int kat_interp_luma(const PIX* ref_plane, int plane_w, int plane_h, int rstride, int pad, int bx, int by, int w, int h, const int16_t* mv,
+                           int n, int bipred, int bitdepth, PIX* out) {
+  if (!ref_plane || !mv || !out || n <= 0) return 1;
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_ref((size_t)rstride * (plane_h + 2 * pad), ref_plane);
+  DevBuf<int16_t> d_mv((size_t)2 * n, mv);
+  DevBuf<PIX> d_o((size_t)n * w * h);
+  hipLaunchKernelGGL(k_kat_interp<PIX>, dim3(n), dim3(64), 0, g_stream, d_ref.get() + (size_t)pad * rstride + pad, rstride, plane_w, plane_h, bx,
+                     by, w, h, d_mv, bipred, bitdepth, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, (size_t)n * w * h * sizeof(PIX));
+  return 0;
+}
+extern "C" int thor_hip_interp_luma(const uint8_t* ref_plane, int plane_w, int plane_h, int rstride, int pad, int bx, int by, int w,
+                                    int h, const int16_t* mv, int n, int bipred, uint8_t* out) {
+  return kat_interp_luma<uint8_t>(ref_plane, plane_w, plane_h, rstride, pad, bx, by, w, h, mv, n, bipred, 8, out);
+}
+extern "C" int thor_hip_interp_luma_hbd(const uint16_t* ref_plane, int plane_w, int plane_h, int rstride, int pad, int bx, int by, int w,
+                                        int h, const int16_t* mv, int n, int bipred, int bitdepth, uint16_t* out) {
+  if (bitdepth < 9 || bitdepth > 12) return 1;
+  return kat_interp_luma<uint16_t>(ref_plane, plane_w, plane_h, rstride, pad, bx, by, w, h, mv, n, bipred, bitdepth, out);
+}
+
+template <typename PIX>
+static int kat_code_tu_batch(const PIX* org, const PIX* pred, int size, int qp, int coeff_type, int fast, int n, int bitdepth, int16_t* coefq,
+                             PIX* rec, int* cbp) {
+  if (!org || !pred || !coefq || !rec || !cbp || n <= 0) return 1;
+  if (size != 4 && size != 8 && size != 16 && size != 32 && size != 64 && size != 128) return 2;
+  if (!ensure_init_any()) return 3;
+  const size_t px = (size_t)n * size * size;
+  const int qs = size < 16 ? size : 16;
+  DevBuf<PIX> d_org(px, org), d_pred(px, pred), d_rec(px);
+  DevBuf<int16_t> d_cq((size_t)n * qs * qs);
+  DevBuf<int> d_cbp(n);
+  hipLaunchKernelGGL(k_kat_tu<PIX>, dim3(n), dim3(64), 0, g_stream, d_org, d_pred, size, qp, coeff_type, fast, bitdepth, d_cq, d_rec,
+                     d_cbp);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(coefq, d_cq, (size_t)n * qs * qs * 2);
+  backend::d2h(rec, d_rec, px * sizeof(PIX));
+  backend::d2h(cbp, d_cbp, (size_t)n * 4);
+  return 0;
+}
+extern "C" int thor_hip_code_tu_batch(const uint8_t* org, const uint8_t* pred, int size, int qp, int coeff_type, int fast, int n,
+                                      int16_t* coefq, uint8_t* rec, int* cbp) {
+  return kat_code_tu_batch<uint8_t>(org, pred, size, qp, coeff_type, fast, n, 8, coefq, rec, cbp);
+}
+extern "C" int thor_hip_code_tu_batch_hbd(const uint16_t* org, const uint16_t* pred, int size, int qp, int coeff_type, int fast, int n,
+                                          int bitdepth, int16_t* coefq, uint16_t* rec, int* cbp) {
+  if (bitdepth < 9 || bitdepth > 12) return 1;
+  return kat_code_tu_batch<uint16_t>(org, pred, size, qp, coeff_type, fast, n, bitdepth, coefq, rec, cbp);
+}
+
+template <typename PIX> static int kat_deblock_frame(PIX* yuv, int width, int height, int qp, int bitdepth, const thor_hip_cell* cells) {
+  static_assert(sizeof(thor_hip_cell) == sizeof(DbCell), "thor_hip_cell must mirror tk::DbCell");
+  if (!yuv || !cells || width % 8 || height % 8 || width < 16 || height < 16 || qp < 0 || qp > 51) return 1;
+  if (!ensure_init_any()) return 3;
+  DevFrame<PIX> f;
+  f.alloc(width, height, 0);
+  DevBuf<DbCell> d_cells((size_t)(width / 4) * (height / 4), (const DbCell*)cells);
+  upload_yuv(f, yuv, width, height);
+  FrameJob<PIX> J;
+  memset(&J, 0, sizeof(J));
+  J.cfg.width = width; J.cfg.height = height; J.cfg.bitdepth = bitdepth;
+  J.qp = qp; J.rec = f.p; J.cells = d_cells; J.cell_stride = width / 4;
+  DevBuf<FrameJob<PIX>> d_job(1, &J);
+  backend::run_deblock<PIX>(d_job, &J, 1);
+  backend::dev_sync();
+  download_yuv(f, yuv, width, height);
+  f.release();
+  return 0;
+}
+extern "C" int thor_hip_deblock_frame(uint8_t* yuv, int width, int height, int qp, const thor_hip_cell* cells) {
+  return kat_deblock_frame<uint8_t>(yuv, width, height, qp, 8, cells);
+}
+extern "C" int thor_hip_deblock_frame_hbd(uint16_t* yuv, int width, int height, int qp, int bitdepth, const thor_hip_cell* cells) {
+  if (bitdepth < 9 || bitdepth > 12) return 1;
+  return kat_deblock_frame<uint16_t>(yuv, width, height, qp, bitdepth, cells);
+}
+
+// ---- round 6: known-answer entry points for intra prediction, inter prediction of a whole block (luma + chroma, quadrant split), the
+// bi-prediction average, chroma-from-luma, the CDEF direction search / filter, CLPF and the temporally interpolated reference --------------
+namespace {
+template <typename PIX>
+int kat_intra(const PIX* plane, int width, int height, int stride, int bitdepth, int size, int tb_split, int n, const int* par, const PIX* rblocks, PIX* out) {
+  if (!plane || !par || !out || n <= 0 || size < 4 || size > 64 || (size & (size - 1)) || (tb_split && !rblocks) || stride < width) return 1;
+  const int cbs = tb_split ? 2 * size : size;
+  for (int i = 0; i < n; i++) {
+    const int* q = par + 7 * i;
+    if (q[0] < 0 || q[1] < 0 || q[0] + cbs > height || q[1] + cbs > width || q[4] < 0 || q[5] < 0 || q[6] < 0 || q[5] + size > cbs || q[6] + size > cbs) return 2;
+    if ((q[2] && q[1] + 2 * cbs > width) || (q[3] && q[0] + 2 * cbs > height)) return 2;   // up-right / down-left samples must exist
+  }
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_p((size_t)stride * height, plane);
+  DevBuf<int> d_par((size_t)7 * n, par);
+  DevBuf<PIX> d_rb(tb_split ? (size_t)n * cbs * cbs : 0, tb_split ? rblocks : nullptr);   // without tb_split the kernel does not read it
+  DevBuf<PIX> d_o((size_t)n * size * size);
+  hipLaunchKernelGGL(k_kat_intra<PIX>, dim3(n), dim3(64), 0, g_stream, d_p, stride, bitdepth, size, tb_split, d_par, d_rb, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, (size_t)n * size * size * sizeof(PIX));
+  return 0;
+}
+// frame with the reference windows' replicate padding (what k_make_ref produces from a reconstruction)
+template <typename PIX> DevFrame<PIX> kat_padded_ref(const PIX* yuv, int width, int height) {
+  DevFrame<PIX> rec, ref;
+  rec.alloc(width, height, 0);
+  ref.alloc(width, height, kPadY);
+  upload_yuv(rec, yuv, width, height);
+  FrameJob<PIX> J;
+  memset(&J, 0, sizeof(J));
+  J.cfg.width = width; J.cfg.height = height; J.rec = rec.p;
+  backend::run_make_ref<PIX>(&J, &ref.p, 1);
+  backend::dev_sync();
+  rec.release();
+  return ref;
+}
+template <typename PIX>
+int kat_inter_yuv(const PIX* yuv, int width, int height, int bitdepth, int size, int n, const int* par, const int16_t* mv, PIX* out) {
+  if (!yuv || !par || !mv || !out || n <= 0 || size < 8 || size > 128 || (size & (size - 1)) || width % 8 || height % 8) return 1;
+  for (int i = 0; i < n; i++) {
+    const int* q = par + 5 * i;
+    if (q[0] < 0 || q[1] < 0 || q[0] + size > height || q[1] + size > width || (q[4] && size < 16)) return 2;
+  }
+  if (!ensure_init_any()) return 3;
+  DevFrame<PIX> ref = kat_padded_ref(yuv, width, height);
+  DevBuf<int> d_par((size_t)5 * n, par);
+  DevBuf<int16_t> d_mv((size_t)8 * n, mv);
+  const size_t per = (size_t)size * size * 3 / 2;
+  DevBuf<PIX> d_o(per * n);
+  hipLaunchKernelGGL(k_kat_inter_yuv<PIX>, dim3(n), dim3(64), 0, g_stream, ref.p, width, height, bitdepth, size, d_par, d_mv, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, per * n * sizeof(PIX));
+  ref.release();
+  return 0;
+}
+template <typename PIX> int kat_average(const PIX* a, const PIX* b, int size, int n, PIX* out) {
+  if (!a || !b || !out || n <= 0 || size < 8 || size > 128 || (size & (size - 1))) return 1;
+  if (!ensure_init_any()) return 3;
+  const size_t tot = (size_t)n * size * size * 3 / 2;
+  DevBuf<PIX> d_a(tot, a), d_b(tot, b), d_o(tot);
+  hipLaunchKernelGGL(k_kat_average<PIX>, dim3(n), dim3(64), 0, g_stream, d_a, d_b, size, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, tot * sizeof(PIX));
+  return 0;
+}
+template <typename PIX> int kat_cfl(const PIX* y, PIX* uv, const PIX* ry, int nl, int bitdepth, int n) {
+  if (!y || !uv || !ry || n <= 0 || nl < 8 || nl > 128 || (nl & (nl - 1))) return 1;
+  if (!ensure_init_any()) return 3;
+  const size_t ny = (size_t)n * nl * nl, nc = (size_t)n * 2 * (nl / 2) * (nl / 2);
+  DevBuf<PIX> d_y(ny, y), d_r(ny, ry), d_uv(nc, uv);
+  hipLaunchKernelGGL(k_kat_cfl<PIX>, dim3(n), dim3(64), 0, g_stream, d_y, d_uv, d_r, nl, bitdepth);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(uv, d_uv, nc * sizeof(PIX));
+  return 0;
+}
+template <typename PIX> int kat_cdef_dir(const PIX* blocks, int bitdepth, int n, int* dir, int* var) {
+  if (!blocks || !dir || !var || n <= 0) return 1;
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_b((size_t)n * 64, blocks);
+  DevBuf<int> d_d(n), d_v(n);
+  hipLaunchKernelGGL(k_kat_cdef_dir<PIX>, dim3((n + 63) / 64), dim3(64), 0, g_stream, d_b, n, bitdepth - 8, d_d, d_v);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(dir, d_d, (size_t)n * 4); backend::d2h(var, d_v, (size_t)n * 4);
+  return 0;
+}
+template <typename PIX> int kat_cdef_filter(const PIX* plane, int w, int h, int stride, int bitdepth, int bsize, int n, const int* par, PIX* out) {
+  if (!plane || !par || !out || n <= 0 || (bsize != 4 && bsize != 8) || stride < w) return 1;
+  for (int i = 0; i < n; i++) {
+    const int* q = par + 7 * i;
+    if (q[0] < 0 || q[1] < 0 || q[0] + bsize > w || q[1] + bsize > h || q[4] < 0 || q[4] > 7) return 2;
+  }
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_p((size_t)stride * h, plane);
+  DevBuf<int> d_par((size_t)7 * n, par);
+  DevBuf<PIX> d_o((size_t)n * bsize * bsize);
+  hipLaunchKernelGGL(k_kat_cdef_filter<PIX>, dim3(n), dim3(64), 0, g_stream, d_p, w, h, stride, bsize, bitdepth - 8, d_par, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, (size_t)n * bsize * bsize * sizeof(PIX));
+  return 0;
+}
+// CLPF: the two device passes of the product (statistics per 8x8 block, filter per 8x8 luma / 4x4 chroma unit) on one frame.
+template <typename PIX>
+int kat_clpf(const PIX* rec_yuv, const PIX* org_yuv, int width, int height, int bitdepth, int qp, const thor_hip_cell* cells, const int* strength, int fb_log2,
+             const uint8_t* fb_on, uint32_t* stats, PIX* out_yuv) {
+  if (!rec_yuv || !org_yuv || !cells || !strength || !fb_on || !stats || !out_yuv || width % 16 || height % 16 || fb_log2 < 5 || fb_log2 > 7) return 1;
+  if (!ensure_init_any()) return 3;
+  DevFrame<PIX> rec, src, org;
+  rec.alloc(width, height, 0); src.alloc(width, height, 0); org.alloc(width, height, 0);
+  upload_yuv(rec, rec_yuv, width, height); upload_yuv(src, rec_yuv, width, height); upload_yuv(org, org_yuv, width, height);
+  DevBuf<DbCell> d_cells((size_t)(width / 4) * (height / 4), (const DbCell*)cells);
+  const int nblk = (width / 8) * (height / 8) + 2 * (width / 16) * (height / 16);
+  const int nfb = ((width + (1 << fb_log2) - 1) >> fb_log2) * ((height + (1 << fb_log2) - 1) >> fb_log2);
+  DevBuf<uint32_t> d_stats((size_t)4 * nblk);
+  DevBuf<uint8_t> d_on((size_t)nfb, fb_on);
+  ClpfJob<PIX> J;
+  memset(&J, 0, sizeof(J));
+  J.rec = rec.p; J.src = src.p; J.org = org.p; J.width = width; J.height = height; J.bitdepth = bitdepth; J.qp = qp;
+  J.cells = d_cells; J.cs = width / 4; J.stats = d_stats;
+  for (int k = 0; k < 3; k++) J.strength[k] = strength[k];
+  J.fb_log2 = fb_log2; J.fb_on = d_on;
+  DevBuf<ClpfJob<PIX>> d_job(1, &J);
+  backend::run_clpf_stats<PIX>(d_job, &J, 1);
+  backend::run_clpf_apply<PIX>(d_job, &J, 1);
+  backend::dev_sync();
+  backend::d2h(stats, d_stats, (size_t)4 * nblk * 4);
+  download_yuv(rec, out_yuv, width, height);
+  rec.release(); src.release(); org.release();
+  return 0;
+}
+// interpolate_frames(new, ref0, ref1, 2, 1) (common/temporal_interp.c:909) through the engine's own path (Engine::make_interp_frames, tk_interp_dev.h)
+template <typename PIX> int kat_interpolate(const PIX* yuv0, const PIX* yuv1, int width, int height, int bitdepth, PIX* out_yuv) {
+  if (!yuv0 || !yuv1 || !out_yuv || width % 8 || height % 8 || width < 64 || height < 64) return 1;
+  if (!ensure_init_any()) return 3;
+  SeqParams sp;
+  sp.width = width; sp.height = height; sp.bitdepth = bitdepth; sp.input_bitdepth = bitdepth;
+  sp.num_reorder_pics = 7; sp.interp_ref = 1; sp.max_num_ref = 2; sp.HQperiod = 8; sp.cdef = 0; sp.clpf = 0;
+  Engine<PIX>* eng = new Engine<PIX>();
+  eng->open(sp, 1);
+  Stream<PIX>& q = eng->st[0];
+  for (int k = 0; k < 2; k++) {
+    upload_yuv(q.rec, k ? yuv1 : yuv0, width, height);
+    FrameJob<PIX> J;
+    memset(&J, 0, sizeof(J));
+    J.cfg.width = width; J.cfg.height = height; J.rec = q.rec.p;
+    backend::run_make_ref<PIX>(&J, &q.ring[k].p, 1);
+    backend::dev_sync();
+  }
+  std::vector<FrameParams> fp(1);
+  fp[0].interp_ref = 1; fp[0].interp_src[0] = 0; fp[0].interp_src[1] = 1; fp[0].frame_num = 1;
+  eng->make_interp_frames(fp, 0, 1);
+  backend::dev_sync();
+  download_yuv(q.interp, out_yuv, width, height);
+  eng->close();
+  delete eng;
+  return 0;
+}
+}  // namespace
+#define KAT_BD(call8, call16) do { if (bitdepth == 8) return call8; if (bitdepth >= 9 && bitdepth <= 12) return call16; return 1; } while (0)
+extern "C" int thor_hip_kat_intra(const void* plane, int width, int height, int stride, int bitdepth, int size, int tb_split, int n, const int* par,
+                                  const void* rblocks, void* out) {
+  KAT_BD(kat_intra<uint8_t>((const uint8_t*)plane, width, height, stride, 8, size, tb_split, n, par, (const uint8_t*)rblocks, (uint8_t*)out),
+         kat_intra<uint16_t>((const uint16_t*)plane, width, height, stride, bitdepth, size, tb_split, n, par, (const uint16_t*)rblocks, (uint16_t*)out));
+}
+extern "C" int thor_hip_kat_inter_yuv(const void* yuv, int width, int height, int bitdepth, int size, int n, const int* par, const int16_t* mv, void* out) {
+  KAT_BD(kat_inter_yuv<uint8_t>((const uint8_t*)yuv, width, height, 8, size, n, par, mv, (uint8_t*)out),
+         kat_inter_yuv<uint16_t>((const uint16_t*)yuv, width, height, bitdepth, size, n, par, mv, (uint16_t*)out));
+}
+extern "C" int thor_hip_kat_average(const void* a, const void* b, int size, int bitdepth, int n, void* out) {
+  KAT_BD(kat_average<uint8_t>((const uint8_t*)a, (const uint8_t*)b, size, n, (uint8_t*)out),
+         kat_average<uint16_t>((const uint16_t*)a, (const uint16_t*)b, size, n, (uint16_t*)out));
+}
+extern "C" int thor_hip_kat_cfl(const void* y, void* uv, const void* ry, int n_luma, int bitdepth, int n) {
+  KAT_BD(kat_cfl<uint8_t>((const uint8_t*)y, (uint8_t*)uv, (const uint8_t*)ry, n_luma, 8, n),
+         kat_cfl<uint16_t>((const uint16_t*)y, (uint16_t*)uv, (const uint16_t*)ry, n_luma, bitdepth, n));
+}
+extern "C" int thor_hip_kat_cdef_dir(const void* blocks, int bitdepth, int n, int* dir, int* var) {
+  KAT_BD(kat_cdef_dir<uint8_t>((const uint8_t*)blocks, 8, n, dir, var), kat_cdef_dir<uint16_t>((const uint16_t*)blocks, bitdepth, n, dir, var));
+}
+extern "C" int thor_hip_kat_cdef_filter(const void* plane, int width, int height, int stride, int bitdepth, int bsize, int n, const int* par, void* out) {
+  KAT_BD(kat_cdef_filter<uint8_t>((const uint8_t*)plane, width, height, stride, 8, bsize, n, par, (uint8_t*)out),
+         kat_cdef_filter<uint16_t>((const uint16_t*)plane, width, height, stride, bitdepth, bsize, n, par, (uint16_t*)out));
+}
+extern "C" int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int width, int height, int bitdepth, int qp, const thor_hip_cell* cells,
+                                 const int* strength, int fb_log2, const uint8_t* fb_on, uint32_t* stats, void* out_yuv) {
+  KAT_BD(kat_clpf<uint8_t>((const uint8_t*)rec_yuv, (const uint8_t*)org_yuv, width, height, 8, qp, cells, strength, fb_log2, fb_on, stats, (uint8_t*)out_yuv),
+         kat_clpf<uint16_t>((const uint16_t*)rec_yuv, (const uint16_t*)org_yuv, width, height, bitdepth, qp, cells, strength, fb_log2, fb_on, stats, (uint16_t*)out_yuv));
+}
+// Per-plane SSE of two host frames through k_frame_sse (the kernel the engine launches with frame distortion on).
+template <typename PIX> int frame_sse_host(const PIX* a, const PIX* b, int width, int height, unsigned long long out[3]) {
+  if (!a || !b || !out || width % 8 || height % 8 || width < 8 || height < 8) return 1;
+  if (!ensure_init_any()) return 3;
+  DevFrame<PIX> fa, fb;
+  fa.alloc(width, height, 0); fb.alloc(width, height, 0);
+  upload_yuv(fa, a, width, height); upload_yuv(fb, b, width, height);
+  FrameJob<PIX> J;
+  memset(&J, 0, sizeof(J));
+  J.cfg.width = width; J.cfg.height = height; J.orig = fa.p; J.rec = fb.p;
+  DevBuf<FrameJob<PIX>> dj(1, &J);
+  DevBuf<unsigned long long> dout(4);  // zeroed
+  launch_frame_sse<PIX>(dj, &J, 1, dout);
+  backend::dev_sync();
+  backend::d2h(out, dout, 3 * sizeof(unsigned long long));
+  fa.release(); fb.release();
+  return 0;
+}
+extern "C" int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth, unsigned long long out[3]) {
+  KAT_BD(frame_sse_host<uint8_t>((const uint8_t*)a, (const uint8_t*)b, w, h, out),
+         frame_sse_host<uint16_t>((const uint16_t*)a, (const uint16_t*)b, w, h, out));
+}
+extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
+  KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),
+         kat_interpolate<uint16_t>((const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, (uint16_t*)out_yuv));
+}
+
+// Resources of the superblock kernel as the runtime sees them (a guard against silent occupancy regressions: round 6 found the 8-bit kernel at 227 VGPRs =
+// two workgroups per CU after an unrelated kernel had raised the register budget of a shared __noinline__ function).
+extern "C" int thor_hip_superblock_kernel_info(int sample_bytes, int* num_regs, int* lds_bytes, int* private_bytes, int* workgroups_per_cu) {
+  if (!ensure_init_any()) return 3;
+  hipFuncAttributes a;
+  int per_cu = 0;
+  if (sample_bytes == 1) {
+    HIPCHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_superblocks<uint8_t>)));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_superblocks<uint8_t>, kWgThreads, 0));
+  } else if (sample_bytes == 2) {
+    HIPCHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_superblocks<uint16_t>)));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_superblocks<uint16_t>, kWgThreads, 0));
+  } else if (sample_bytes == 0) {   // the latency build of the 8-bit kernel (thor_hip_lat.cpp)
+    if (thor_lat_kernel_info(num_regs, lds_bytes, private_bytes)) return 2;
+    if (workgroups_per_cu) *workgroups_per_cu = thor_lat_workgroups_per_cu();
+    return 0;
+  } else if (sample_bytes == 3) {   // the eight-wavefront build of the 8-bit kernel (thor_hip_wide.cpp)
+    if (thor_wide_kernel_info(num_regs, lds_bytes, private_bytes)) return 2;
+    if (workgroups_per_cu) *workgroups_per_cu = thor_wide_workgroups_per_cu();
+    return 0;
+  } else return 1;
+  if (num_regs) *num_regs = a.numRegs;
+  if (lds_bytes) *lds_bytes = (int)a.sharedSizeBytes;
+  if (private_bytes) *private_bytes = (int)a.localSizeBytes;
+  if (workgroups_per_cu) *workgroups_per_cu = per_cu;
+  return 0;
+}
+// Which build of the 8-bit superblock kernel the engine configured last launches with: 0 throughput (thor_hip.cpp), 1 latency (thor_hip_lat.cpp), 2 eight
+// wavefronts per workgroup (thor_hip_wide.cpp).  Decided at the engine's first launch from the number of streams and the geometry (run_superblocks).
+extern "C" int thor_hip_superblock_kernel_in_use(void) { return tk::backend::g_last_kern; }

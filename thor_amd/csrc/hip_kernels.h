@@ -1,0 +1,185 @@
+// hip_kernels.h - the frame-level kernels of the throughput build (part of the translation unit thor_hip.cpp, device-only): deblocking, padded
+// reference, frame SSE, bit gather, CDEF, CLPF, the temporally interpolated reference.  Launched by hip_backend.h.
+// The dependency-driven persistent superblock kernel is not here: a task is (stream, superblock), SB(k,l) needs its left neighbour (k,l-1) and its
+// up-right neighbour (k-1,l+1) ((k-1,l) in the last column) - SURVEY.md Appendix A; the kernel is in tk_kernel.h, its ready-task queue in tk_sched.h.
+#pragma once
+namespace tk {
+
+template <typename PIX> __global__ void k_deblock(const FrameJob<PIX>* jobs, int pass) {
+  const FrameJob<PIX>& J = jobs[blockIdx.y];
+  DbParams P;
+  P.width = J.cfg.width; P.height = J.cfg.height; P.bitdepth = J.cfg.bitdepth;
+  const int qpc = g_tab.chroma_qp[J.qp];
+  P.beta = g_tab.beta[J.qp] << (P.bitdepth - 8);
+  P.tc_y = g_tab.tc[J.qp] >> (12 - P.bitdepth);
+  P.tc_c = g_tab.tc[qpc] >> (12 - P.bitdepth);
+  P.cells = J.cells; P.cs = J.cell_stride;
+  deblock_pass(J.rec, P, pass, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x));
+}
+
+template <typename PIX> struct RefJob { Plane3<PIX> rec, ref; int width, height; };
+template <typename PIX> __global__ void k_make_ref(const RefJob<PIX>* rj) {
+  const RefJob<PIX>& R = rj[blockIdx.y];
+  make_ref_rows(R.rec, R.ref, R.width, R.height, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, (int)blockDim.x);
+}
+
+// Per-plane SSE of the final reconstruction against the original (frame_sse_rows), streams along y: each wavefront takes rows
+// (blockIdx.x * 4 + wave, + 4 * gridDim.x, ...), sums its lanes' 64-bit partials with DPP and adds them to the stream's slots with one
+// 64-bit atomic per plane.  Integer sums: the result does not depend on the order.
+template <typename PIX> __global__ __launch_bounds__(256) void k_frame_sse(const FrameJob<PIX>* jobs, unsigned long long* out) {
+  const FrameJob<PIX>& J = jobs[blockIdx.y];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  unsigned long long acc[3] = {0, 0, 0};
+  frame_sse_rows(J.orig, J.rec, J.cfg.width, J.cfg.height, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64, acc);
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long v = wave_sum64_dpp(acc[k]);
+    if (lane == 0 && v) atomicAdd(&out[4 * (size_t)blockIdx.y + k], v);
+  }
+}
+
+// Bit-level concatenation: one workgroup per item.  dst is zero-filled; words are OR-ed in.
+__global__ void k_gather_bits(const backend::GatherItem* items, int n, uint32_t* dst) {
+  const int it = blockIdx.x;
+  if (it >= n) return;
+  const backend::GatherItem g = items[it];
+  const int nw = (g.nbits + 31) >> 5;
+  const int sh = (int)(g.dst_bit & 31);
+  const long long w0 = g.dst_bit >> 5;
+  for (int j = threadIdx.x; j < nw; j += blockDim.x) {
+    uint32_t v = g.src[j];
+    const int valid = g.nbits - 32 * j;           // bits of this word that belong to the string
+    if (valid < 32) v &= ~((1u << (32 - valid)) - 1u);
+    if (sh == 0) atomicOr(&dst[w0 + j], v);
+    else {
+      atomicOr(&dst[w0 + j], v >> sh);
+      const uint32_t lo = v << (32 - sh);
+      if (lo) atomicOr(&dst[w0 + j + 1], lo);
+    }
+  }
+}
+
+template <typename PIX> __global__ void k_copy_planes(const CdefJob<PIX>* cj) {
+  const CdefJob<PIX>& C = cj[blockIdx.y];
+  const int rows = C.height + C.height;  // Y rows + U rows + V rows
+  for (int it = blockIdx.x; it < rows; it += gridDim.x) {
+    const PIX* s; PIX* d; int w;
+    if (it < C.height) { s = C.rec.y + (size_t)it * C.rec.sy; d = C.src.y + (size_t)it * C.src.sy; w = C.width; }
+    else if (it < C.height + C.height / 2) { int r = it - C.height; s = C.rec.u + (size_t)r * C.rec.sc; d = C.src.u + (size_t)r * C.src.sc; w = C.width / 2; }
+    else { int r = it - C.height - C.height / 2; s = C.rec.v + (size_t)r * C.rec.sc; d = C.src.v + (size_t)r * C.src.sc; w = C.width / 2; }
+    for (int x = threadIdx.x; x < w; x += blockDim.x) d[x] = s[x];
+  }
+}
+// passes 0 (flags), 1 (direction / variance per 8x8 block) and 4 (apply) of CDEF: one instance per pass, so that each gets its own register allocation
+template <typename PIX, int PASS> __global__ __launch_bounds__(256) void k_cdef(const CdefJob<PIX>* cj) {   // (no bound = 1024 threads = a 128-VGPR cap: the apply pass spilled 30)
+  const CdefJob<PIX>& C = cj[blockIdx.y];
+  const int gid = (int)(blockIdx.x * blockDim.x + threadIdx.x), gsize = (int)(gridDim.x * blockDim.x);
+  if constexpr (PASS == 0) cdef_pass_flags(C, gid, gsize);
+  else if constexpr (PASS == 1) cdef_pass_dir(C, gid, gsize);
+  else cdef_pass_apply(C, gid, gsize);
+}
+// pass 2 of the CDEF search (tk_cdef.h: wavefront form): one wavefront per 8x8 luma-unit block, four independent wavefronts per workgroup (no workgroup
+// barrier: a wavefront whose block is skipped leaves at once)
+template <typename PIX> __global__ __launch_bounds__(256) void k_cdef_mse(const CdefJob<PIX>* cj) {
+  const CdefJob<PIX>& C = cj[blockIdx.y];
+  if (!C.cdef_bits) return;
+  __shared__ CdefWaveWs<PIX> ws[4];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  const int b = (int)blockIdx.x * 4 + wave;
+  if (b >= (C.width / 8) * (C.height / 8)) return;
+  cdef_mse_block_wave(mk_team(lane, 64), C, b, &ws[wave]);
+}
+template <typename PIX> __global__ void k_clpf(const ClpfJob<PIX>* lj, int pass) {
+  const ClpfJob<PIX>& L = lj[blockIdx.y];
+  const int gid = (int)(blockIdx.x * blockDim.x + threadIdx.x), gsize = (int)(gridDim.x * blockDim.x);
+  if (pass == 0) clpf_pass_stats(L, gid, gsize);
+  else clpf_pass_apply(L, gid, gsize);
+}
+template <typename PIX> __global__ void k_clpf_copy(const ClpfJob<PIX>* lj) {  // rec -> src (unfiltered copy)
+  const ClpfJob<PIX>& C = lj[blockIdx.y];
+  const int rows = C.height + C.height;
+  for (int it = blockIdx.x; it < rows; it += gridDim.x) {
+    const PIX* s; PIX* d; int w;
+    if (it < C.height) { s = C.rec.y + (size_t)it * C.rec.sy; d = C.src.y + (size_t)it * C.src.sy; w = C.width; }
+    else if (it < C.height + C.height / 2) { int r = it - C.height; s = C.rec.u + (size_t)r * C.rec.sc; d = C.src.u + (size_t)r * C.src.sc; w = C.width / 2; }
+    else { int r = it - C.height - C.height / 2; s = C.rec.v + (size_t)r * C.rec.sc; d = C.src.v + (size_t)r * C.src.sc; w = C.width / 2; }
+    for (int x = threadIdx.x; x < w; x += blockDim.x) d[x] = s[x];
+  }
+}
+template <typename PIX> __global__ __launch_bounds__(1024) void k_cdef_select(const CdefJob<PIX>* cj) {
+  BlockTeam t{(int)threadIdx.x, (int)blockDim.x};
+  cdef_pass_select(t, cj[blockIdx.x]);
+}
+
+// ---- temporally interpolated reference (tk_interp_dev.h) -----------------------------------------------------------
+template <typename PIX> __global__ void k_interp_clear(const idev::Job<PIX>* jobs) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  const int gid = (int)(blockIdx.x * blockDim.x + threadIdx.x), gsz = (int)(gridDim.x * blockDim.x);
+  for (int l = 0; l < J.levels; l++) {
+    const idev::Level<PIX>& L = J.lv[l];
+    const int cnt = L.bw * L.bh + L.bw + 2;
+    uint32_t* a = (uint32_t*)L.mv[0];
+    uint32_t* b = (uint32_t*)L.mv[1];
+    for (int k = gid; k < cnt; k += gsz) { a[k] = 0; b[k] = 0; }
+    for (int k = gid; k < L.bh / idev::kStep + 1; k += gsz) L.prog[k] = 0;
+  }
+}
+template <typename PIX> __global__ void k_interp_down(const idev::Job<PIX>* jobs, int l) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  if (l >= J.levels) return;
+  const int ow = J.width >> l, oh = J.height >> l, pw = ow + 64;
+  const int total = (oh + 64) * pw;
+  for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < total; k += (int)(gridDim.x * blockDim.x)) {
+    const int i = k / pw - 32, j = k % pw - 32;
+    for (int r = 0; r < 2; r++)
+      idev::down2x2_item(l == 1 ? J.ref[r].y : J.dpic[r][l - 1], l == 1 ? J.ref[r].sy : J.dstride[l - 1], J.dpic[r][l], J.dstride[l], ow, oh, i, j);
+  }
+}
+// One wavefront per 16x16-block row.  Rows are handed out by a ticket, so the row above a wave's row was always taken by
+// a wave that started earlier: the wave waits until that row is two blocks ahead (or finished) and never dead-locks.
+template <typename PIX> __global__ __launch_bounds__(64) void k_interp_estimate(const idev::Job<PIX>* jobs, int lvl) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  if (lvl >= J.levels) return;
+  const idev::Level<PIX>& L = J.lv[lvl];
+  const Team t = mk_team((int)threadIdx.x, 64);
+  int row = 0;
+  if (threadIdx.x == 0) row = (int)atomicAdd((unsigned*)L.ticket, 1u);
+  row = __builtin_amdgcn_readfirstlane(row);
+  const int nrows = L.bh / idev::kStep, ncols = L.bw / idev::kStep;
+  if (row >= nrows) return;
+  for (int c = 0; c < ncols; c++) {
+    if (row > 0) {
+      const int need = c + 2 < ncols ? c + 2 : ncols;
+      while (__hip_atomic_load(&L.prog[row - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) __builtin_amdgcn_s_sleep(8);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    idev::estimate_block(t, L, row * idev::kStep, c * idev::kStep);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (threadIdx.x == 0) __hip_atomic_store(&L.prog[row], c + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+template <typename PIX> __global__ __launch_bounds__(64) void k_interp_merge(const idev::Job<PIX>* jobs, int lvl) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  if (lvl >= J.levels) return;
+  const idev::Level<PIX>& L = J.lv[lvl];
+  const Team t = mk_team((int)threadIdx.x, 64);
+  for (int k = blockIdx.x; k < L.bw * L.bh; k += gridDim.x) idev::merge_block(t, L, k / L.bw, k % L.bw);
+}
+template <typename PIX> __global__ void k_interp_upscale(const idev::Job<PIX>* jobs, int lvl) {  // level lvl -> guide of lvl-1
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  if (lvl >= J.levels || lvl < 1) return;
+  const idev::Level<PIX>& L = J.lv[lvl];
+  const idev::Level<PIX>& O = J.lv[lvl - 1];
+  for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < O.bw * O.bh; k += (int)(gridDim.x * blockDim.x))
+    idev::upscale_item(L.nmv[1], L.bw, O.gmv1, O.bw, k / O.bw, k % O.bw);
+}
+template <typename PIX> __global__ __launch_bounds__(64) void k_interp_mc(const idev::Job<PIX>* jobs) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  const idev::Level<PIX>& L = J.lv[0];
+  const Team t = mk_team((int)threadIdx.x, 64);
+  for (int k = blockIdx.x; k < L.bw * L.bh; k += gridDim.x) idev::mot_comp_unit(t, J, k / L.bw, k % L.bw);
+}
+template <typename PIX> __global__ void k_interp_pad(const idev::Job<PIX>* jobs) {
+  const idev::Job<PIX>& J = jobs[blockIdx.y];
+  idev::pad_item(J, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+}
+}  // namespace tk

@@ -1,6 +1,6 @@
 // tk_altbuild.h - body of an ALTERNATIVE BUILD of the engine sources (tk_*.h): thor_hip_lat.cpp and thor_hip_wide.cpp define the build's parameters
 // (TK_OCC, TK_WAVES), re-name namespace tk (#define tk tk_xxx) and the prefix of the entry points (TK_ALT(name)) and include this file.  Each build is its
-// own translation unit with its own copy of the constant tables; thor_hip.cpp (the throughput build + the whole host side) calls the hidden entry points.
+// own translation unit with its own copy of the constant tables; thor_hip.cpp (the throughput build + the whole host side; hip_backend.h) calls the hidden entry points.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include "tk_kernel.h"
@@ -12,7 +12,7 @@ __device__ Tables g_tab;
 // (internal to libthor_hip.so: hidden symbols, called only by thor_hip.cpp)
 #define TK_INTERNAL __attribute__((visibility("hidden")))
 extern "C" {
-// the constant tables of this copy of the engine (tk_tables.h: filled by the host side of thor_hip.cpp, identical bytes)
+// the constant tables of this copy of the engine (tk_tables.h: filled by hip_backend.h:ensure_init, identical bytes)
 TK_INTERNAL int TK_ALT(upload_tables)(const void* tables, size_t bytes) {
   if (bytes != sizeof(tk::Tables)) return 1;
   return hipMemcpyToSymbol(HIP_SYMBOL(tk::g_tab), tables, bytes) == hipSuccess ? 0 : 2;

@@ -1443,7 +1443,7 @@ TK_DEVNI void md_item_trial(const Team t, JobR<PIX> J, WsP<PIX> ws, MdCtx<PIX>& 
   WgShared* const sh_ = tk_uniform_ptr(M.sh);
   // the reference's search item was taken from the queue before this one: it is finished or running on another wave.  A wait of
   // kWgWaitLimit wall-clock ticks (a search item takes milliseconds) is a protocol error: wg_wait_failed() stops the kernel / the
-  // simulation loudly instead of hanging the GPU (the host reports the aborted launch, thor_hip.cpp:run_superblocks).
+  // simulation loudly instead of hanging the GPU (the host reports the aborted launch, hip_backend.h:run_superblocks).
   const unsigned long long w0 = wg_clock();
   TK_PROFMD_MARK(pwt_);
   for (unsigned spins = 1;; spins++) {

@@ -576,7 +576,7 @@ typedef TK_LDS int16_t lds_i16;
 // SP_GLOBAL, chosen once per block decision) and the leaf loops re-type their pointers with spc<SP>().  Workspace structures
 // that ALWAYS live in LDS on the device (XformWs, MeWs, WgShared, ...) are re-typed with ldsc().  Identity on the host.
 enum { SP_GLOBAL = 0, SP_LDS = 1 };
-// Wavefronts per SIMD the superblock kernel's register allocation is sized for (thor_hip.cpp:k_superblocks): 3 (168 VGPRs, three
+// Wavefronts per SIMD the superblock kernel's register allocation is sized for (tk_kernel.h:k_superblocks): 3 (168 VGPRs, three
 // workgroups per CU, 53 KB of LDS each) or 2 (256 VGPRs, two workgroups per CU, 80 KB of LDS each).
 #ifndef TK_OCC
 #define TK_OCC 3

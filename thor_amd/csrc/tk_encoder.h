@@ -1,6 +1,6 @@
 // tk_encoder.h - host side of the engine: stream state in device memory, per-frame job set-up,
 // superblock wavefront scheduling, bitstream assembly.  Shared by the HIP library (kernels in
-// thor_hip.cpp) and by the 1-lane host simulation used in CPU tests (hostsim.cpp); the two
+// hip_kernels.h / tk_kernel.h, launched by hip_backend.h) and by the 1-lane host simulation used in CPU tests (hostsim.cpp); the two
 // differ only in the `backend` functions declared below.
 // Specification followed: enc/encode_frame.c:637-850 (encode_frame: lambda, header, SB raster
 // order, deblock, CDEF, reference rotation), enc/write_bits.c:49-121 (sequence / frame header),
@@ -45,14 +45,23 @@ template <typename PIX> void run_cdef(const CdefJob<PIX>* cjobs, const CdefJob<P
 // bit-level concatenation of per-SB bit strings: item i copies nbits[i] bits from src[i] to bit offset dst_bit[i] of dst
 struct GatherItem { const uint32_t* src; int nbits; long long dst_bit; };
 void run_gather(const GatherItem* d_items, int n, uint32_t* dst);
-void release_superblocks(const void* jobs);
+void release_superblocks(const void* jobs);  // frees the scheduler state run_superblocks keeps for this job array
 // temporally interpolated reference frames of n streams (all phases: pyramid, block search per level, merge, upscale,
 // motion compensation, padding); jobs/hjobs: device/host arrays of n idev::Job
-template <typename PIX> void run_interp(const idev::Job<PIX>* jobs, const idev::Job<PIX>* hjobs, int n);  // frees the scheduler state run_superblocks keeps for this job array
+template <typename PIX> void run_interp(const idev::Job<PIX>* jobs, const idev::Job<PIX>* hjobs, int n);
+// the launch templates above for one sample type: each backend instantiates them for uint8_t and uint16_t
+#define TK_BACKEND_INSTANTIATE(PIX)                                                                      \
+  template void run_interp<PIX>(const idev::Job<PIX>*, const idev::Job<PIX>*, int);                      \
+  template void run_superblocks<PIX>(const FrameJob<PIX>*, const FrameJob<PIX>*, int, const SbRange*);   \
+  template void run_deblock<PIX>(const FrameJob<PIX>*, const FrameJob<PIX>*, int);                       \
+  template void run_make_ref<PIX>(const FrameJob<PIX>*, const Plane3<PIX>*, int);                        \
+  template void run_cdef<PIX>(const CdefJob<PIX>*, const CdefJob<PIX>*, int);                            \
+  template void run_clpf_stats<PIX>(const ClpfJob<PIX>*, const ClpfJob<PIX>*, int);                      \
+  template void run_clpf_apply<PIX>(const ClpfJob<PIX>*, const ClpfJob<PIX>*, int);
 }  // namespace backend
 #if !TK_HOST
 // Per-plane sums of squared differences orig - rec of S streams into out[4 * s + plane] (added: the caller clears the slots), one launch
-// (thor_hip.cpp: k_frame_sse).  The host build calls frame_sse_rows directly (Engine::finish_frames).
+// (hip_kernels.h: k_frame_sse, launched by hip_backend.h).  The host build calls frame_sse_rows directly (Engine::finish_frames).
 template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const FrameJob<PIX>* hjobs, int S, unsigned long long* out);
 #endif
 

@@ -1,7 +1,7 @@
 // tk_kernel.h - the persistent, dependency-driven superblock kernel (one workgroup of kWaves wavefronts per superblock in flight; ready-task queue in
 // tk_sched.h).  Its own header since round 6: the engine sources are compiled twice - thor_hip.cpp with the register budget of three wavefronts per SIMD
 // (168 VGPRs, the throughput operating point: 768 resident workgroups) and thor_hip_lat.cpp with that of two (256 VGPRs: no register-pressure spills,
-// 80 KB of LDS per workgroup = search windows for PUs up to 64x64), which the backend launches when a run cannot fill more than two workgroups per CU
+// 80 KB of LDS per workgroup = search windows for PUs up to 64x64), which the backend (hip_backend.h:run_superblocks) launches when a run cannot fill more than two workgroups per CU
 // anyway (few streams: the single-stream / drop-in operating point).
 #pragma once
 #include "tk_block.h"

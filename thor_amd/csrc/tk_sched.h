@@ -1,4 +1,4 @@
-// tk_sched.h - ready-task queues of the persistent superblock kernel (thor_hip.cpp:k_superblocks).
+// tk_sched.h - ready-task queues of the persistent superblock kernel (tk_kernel.h:k_superblocks).
 //
 // SB(k,l) of a stream needs SB(k,l-1) and SB(k-1,l+1) of the same stream (enc/encode_frame.c walks the superblocks in raster
 // order; the dependencies are those of the motion-vector / intra / context neighbours).  One launch per
