@@ -1,7 +1,7 @@
 #!/bin/bash
 # Data-race check of the wave-parallel block decision: 4-wave host simulation (one OS thread per wavefront of a workgroup:
 # work queue, shared minimum key, lock-step bi-prediction, snapshots) under ThreadSanitizer.
-# Expected reports: only the host-only debug counters g_prune_stat (tk_block.h, #if TK_HOST).
+# Expected reports: only the host-only debug counters g_prune_stat (tk_block_rd.h, #if TK_HOST).
 set -e
 cd "$(dirname "$0")/.."
 g++ -std=c++17 -O1 -g -fno-strict-aliasing -fsanitize=thread -DTHOR_HOSTSIM -DTHOR_HOSTSIM_WAVES=4 -ffp-contract=off -pthread -o /tmp/hostsim_tsan_w4 tests/hostsim/hostsim.cpp

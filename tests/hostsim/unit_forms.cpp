@@ -69,7 +69,7 @@ template <typename PIX> static void test_blocks(int bitdepth, unsigned seed) {
       const unsigned long long got = ssd_total(t, ssd_part<SP_GLOBAL, PIX>(t, a, size, b, size, size, size));
       // The modular form is exact while ONE LANE's share stays below 2^32: on the device a lane holds at most 128*128/64 = 256 samples
       // (256 x 4095^2 < 2^32, always exact).  A team smaller than a wavefront (this 1-lane team sums the whole block in one lane) takes the
-      // 64-bit sample loop for blocks of 16-bit samples whose share can exceed that (round 5, tk_block.h:ssd_part): exact for every case.
+      // 64-bit sample loop for blocks of 16-bit samples whose share can exceed that (round 5, tk_block_rd.h:ssd_part): exact for every case.
       CHECK(got == want, "ssd size %d bd %d mode %d: %llu != %llu", size, bitdepth, mode, got, want);
       // truncating average
       average_yuv<SP_GLOBAL, PIX>(t, d, d + size * size, d + size * size * 5 / 4, a, a, a, b, b, b, size, size, size);   // chroma views overlap on purpose: only luma is checked

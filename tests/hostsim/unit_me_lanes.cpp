@@ -1,4 +1,4 @@
-// unit_me_lanes.cpp - TEST INFRASTRUCTURE ONLY.  The motion search with one lane per candidate (tk_me.h: me_cand_fullpel / me_cand8_subpel, taken
+// unit_me_lanes.cpp - TEST INFRASTRUCTURE ONLY.  The motion search with one lane per candidate (tk_me_lanes.h: me_cand_fullpel / me_cand8_subpel, taken
 // by teams of 64 lanes for 8-bit PUs of up to 32x32 samples) against the generic search (every other team size) on the CPU: the product's
 // motion_estimate runs the same sequence of searches twice - once with a team of 64 lanes (64 OS threads, the cross-lane primitives go through the
 // exchange below) and once with a 1-lane team - and vector and cost of every search must be equal.  On the MI355X the same comparison is made inside

@@ -1,4 +1,4 @@
-"""The motion search with one lane per candidate (tk_me.h: me_cand_fullpel / me_cand8_subpel - what 64-lane teams run for PUs of up to 32x32
+"""The motion search with one lane per candidate (tk_me_lanes.h: me_cand_fullpel / me_cand8_subpel - what 64-lane teams run for PUs of up to 32x32
 samples, i.e. what the MI355X runs; round 6: the full-pel passes on 16-bit samples too - 1008 more searches at bitdepth 10) against the generic search on the CPU: tests/hostsim/unit_me_lanes.cpp runs the product's motion_estimate over the
 same sequences of searches with a team of 64 lanes (64 OS threads) and with a 1-lane team; vector and cost of every search must be equal (twelve PU
 shapes x six variants - plain, reference "in the future", the other filter set, no staged window, one long candidate list with a large lambda, a small

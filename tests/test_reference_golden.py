@@ -51,7 +51,7 @@ def test_engine_multi_lane_host_simulation_matches_golden(name):
                                   '192x128_n5_q32_hdb16_gop4_10bit', '208x120_n4_q30_ldb_medium', '208x120_n26_q24_ldb', '192x128_n4_q32_12bit'])
 def test_engine_multi_wave_host_simulation_matches_golden(name):
     """Workgroups of 4 wavefronts (one OS thread each): the block decision of the encoder_speed 0 operating points is
-    spread over the waves through a work queue (tk_block.h:mode_decision_par) - fork/join barriers, atomics on the shared
+    spread over the waves through a work queue (tk_block_queue.h:mode_decision_par) - fork/join barriers, atomics on the shared
     state and key-based pruning run under real concurrency; the result must not depend on the interleaving."""
     c = G[name]
     for _ in range(2):
@@ -85,7 +85,7 @@ def test_sixteen_lane_teams_search_window_and_row_segments_vs_live_reference():
 @needs_ref
 def test_sixty_four_lane_teams_run_the_lane_per_candidate_search_vs_live_reference():
     """64-lane teams (the device's team size) on a 64x64 clip (I + 2 P; the second P frame searches two references and their bi-prediction): with 64 lanes the 8-bit PUs of up to
-    32x32 samples take the lane-per-candidate search (tk_me.h: me_cand_fullpel / me_cand8_subpel) - the code the MI355X runs - inside a complete
+    32x32 samples take the lane-per-candidate search (tk_me_lanes.h: me_cand_fullpel / me_cand8_subpel) - the code the MI355X runs - inside a complete
     encode, on the CPU; stream and reconstruction must equal the live reference run.  (A whole small golden, 192x128 x 3 frames, was run this way once
     in round 5: profiles/r05_hostsim_l64.log - 64 OS threads per team make it too slow for the suite.)"""
     from thor_amd import synth

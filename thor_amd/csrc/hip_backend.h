@@ -202,7 +202,7 @@ template <typename PIX> void run_superblocks(const FrameJob<PIX>* jobs, const Fr
   HIPCHECK(hipMemcpyAsync(&hc, D.ctl, sizeof(hc), hipMemcpyDeviceToHost, g_stream));
   if (hipError_t e = hipStreamSynchronize(g_stream)) {
     // an aborted launch: the kernel traps when a wavefront waits for another wave of its workgroup beyond kWgWaitLimit
-    // (tk_block.h:md_item_trial - a protocol error of the block decision's work queue, never a matter of load)
+    // (tk_block_queue.h:wg_wait_at_least - a protocol error of the block decision's work queue, never a matter of load)
     fprintf(stderr, "Run-time error...\nthor_hip: k_superblocks was aborted: %s (a trap inside the kernel = an intra-workgroup wait that did not end)\n...now exiting to system...\n",
             hipGetErrorString(e));
     abort();

@@ -7,7 +7,7 @@ namespace tk {
 template <typename PIX>
 __global__ __launch_bounds__(64) void k_kat_sad(const PIX* org, int w, int h, const PIX* refp, int rstride, int bx, int by, const int* cand, int n,
                                                uint32_t* out) {
-  // the product's full-pel evaluator (tk_me.h:seg_sads, row segment per lane), plane reads only (no search window)
+  // the product's full-pel evaluator (tk_me_seg.h:seg_sads, row segment per lane), plane reads only (no search window)
   const Team t = mk_team((int)threadIdx.x, 64);
   struct KC { const PIX* p; int dx, dy; };
   MeWin win;

@@ -189,7 +189,7 @@ TK_DEVNI void bs_coeff_team(BitSink& b, const Team t, const int16_t* coeff, int 
   const IzzRef izzr = izz_ref(t, qsize);
   int v[4];
   int last_pos = 0;
-#pragma unroll
+  TK_UNROLL
   for (int q = 0; q < 4; q++) {
     const int p = q * 64 + t.rank;
     v[q] = p < N ? (int)coeff[izzr.z[p]] : 0;
@@ -394,7 +394,7 @@ TK_DEV BlkParam uniform_blk(const BlkParam& a) {
 
 // The part of write_block that does not depend on the residual: super-mode, intra mode / partition and vector differences /
 // candidate index (enc/write_bits.c:360-470).  bs_block_t starts with it; the RDO trials use its length as the first term of
-// their lower bounds (tk_block.h: PruneCtx::head_bits).
+// their lower bounds (tk_block_rd.h: PruneCtx::head_bits).
 template <bool E> TK_DEV void bs_block_head_t(BitSink& b, const SynCtx& s, const BlkParam& p) {
   const int mode = p.mode;
   bs_super_mode_t<E>(b, s, mode, p.ref0, 0);

@@ -37,7 +37,40 @@
 #if TK_HOST
 #define TK_DEVNI static
 #endif
-// The fork/join functions of a block decision (tk_block.h: md_worker_sp, mode_decision_par) save and restore every callee-saved register of the
+// Loop-unroll hint for the device compiler; the host simulation builds without it.
+#if TK_HOST
+#define TK_UNROLL
+#else
+#define TK_UNROLL _Pragma("unroll")
+#endif
+// Profiling builds (-DTHOR_PROF; with it -DTHOR_PROF_ME / _MD / _SUBPEL re-use counter slots, tk_block_ws.h, and -DTHOR_PROF_NOMACROS compiles
+// the TK_PROF_* marks out) instrument device code only.  Always defined, 0 or 1, like TK_HOST.
+#if defined(THOR_PROF) && !TK_HOST
+#define TK_PROF_DEV 1
+#else
+#define TK_PROF_DEV 0
+#endif
+#if TK_PROF_DEV && !defined(THOR_PROF_NOMACROS)
+#define TK_PROF_MACROS 1
+#else
+#define TK_PROF_MACROS 0
+#endif
+#if TK_PROF_DEV && defined(THOR_PROF_ME)
+#define TK_PROF_ME 1
+#else
+#define TK_PROF_ME 0
+#endif
+#if TK_PROF_DEV && defined(THOR_PROF_MD)
+#define TK_PROF_MD 1
+#else
+#define TK_PROF_MD 0
+#endif
+#if TK_PROF_DEV && defined(THOR_PROF_SUBPEL)
+#define TK_PROF_SUBPEL 1
+#else
+#define TK_PROF_SUBPEL 0
+#endif
+// The fork/join functions of a block decision (tk_block_queue.h: md_worker_sp, mode_decision_par) save and restore every callee-saved register of the
 // 168-VGPR budget (64 VGPRs + 36 SGPRs) on every wave of every decision although their callers keep nothing in them.  -DTK_MDW_INLINE inlines
 // them into the kernel: measured in round 6 (profiles/r06_traffic_attribution.md) - HBM-side traffic -6 % (3 of 20 store instructions per pixel
 // gone), throughput -0.9 %: the scratch traffic is waste, not the limiter, and the calls stay.
@@ -128,7 +161,7 @@ struct BlockTeam {
 // ---------------------------------------------------------------------------------
 // Wg: the wavefronts of one workgroup that cooperate on one superblock.  Wave 0 (the "master") walks the quadtree;
 // the other waves are parked on the workgroup barrier and are woken for the parallel regions of a block decision
-// (tk_block.h:mode_decision_par).  The host simulation runs one OS thread per wave (-DTHOR_HOSTSIM_WAVES=N, 1-lane
+// (tk_block_queue.h:mode_decision_par).  The host simulation runs one OS thread per wave (-DTHOR_HOSTSIM_WAVES=N, 1-lane
 // teams) or a single wave (everything else).
 // ---------------------------------------------------------------------------------
 #if !TK_HOST
@@ -146,7 +179,7 @@ namespace hostwaves { void barrier(); }
 #endif
 struct Wg {
   int wave, nwaves;
-#if !TK_HOST && defined(THOR_PROF)
+#if TK_PROF_DEV
   long long* prof;  // this wave's cycle counters: slot 26 = time spent in workgroup barriers
   __device__ __forceinline__ void barrier() const {
     const long long t0 = (long long)__builtin_readcyclecounter();

@@ -9,7 +9,7 @@
 
 namespace tk {
 // Workgroup = kWaves wavefronts on one superblock: wave 0 walks the quadtree (process_sb), the others are parked on
-// the workgroup barrier and take work items of the block decisions (tk_block.h:mode_decision_par).  3 workgroups of
+// the workgroup barrier and take work items of the block decisions (tk_block_queue.h:mode_decision_par).  3 workgroups of
 // 4 waves per CU = 3 waves per SIMD (168 VGPRs each), 768 workgroups resident on the chip.
 enum { kWgThreads = 64 * kWaves };
 enum { kOcc = TK_OCC };   // wavefronts per SIMD the register allocation is sized for (168 VGPRs); 2 and 4 measured slower (profiles/r02_ab_variants.md)

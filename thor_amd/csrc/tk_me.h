@@ -6,867 +6,13 @@
 // parallel and then picks the winner by scanning costs in the reference's evaluation order with
 // strict '<', which reproduces the sequential tie-breaking exactly.
 #pragma once
-#include "tk_common.h"
-#include "tk_pred.h"
-#include "tk_xform.h"
+// The parts below the searches, in dependency order (definition order inside namespace tk is the order of the code object); the
+// searches themselves - me_stage_cb_window, motion_estimate, motion_estimate_bi - follow here.
+#include "tk_me_seg.h"
+#include "tk_me_lanes.h"
+#include "tk_me_fastsub.h"
 
 namespace tk {
-
-enum { kMeWideChunk = 12, kMeMaxCand = kMeWideChunk * 5 };  // 5-offset SADs are evaluated 12 candidates at a time
-
-// per-SB candidate lists (frame_info.mvcand[], enc/mainenc.h:146-148), reset per SB.  One instance per workgroup:
-// the list of reference r is only ever touched by the wavefront that is searching reference r at that moment.
-struct MeLists {
-  mv_t mvcand[kMaxRefs][64];
-  int mvcand_num[kMaxRefs];
-  unsigned long long mvcand_mask[kMaxRefs];
-  int best_ref;  // frame_info.best_ref (enc/mainenc.h:143): per-SB state of the encoder_speed 2 reference shortcut
-};
-struct MeWs {  // per wavefront
-  int sad[kMeMaxCand];
-  mv_t cmv[64];
-  MeLists* lists;
-  long long* prof;
-  uint32_t* win;  // per-wave LDS for the search window (see MeWin below), nullptr: none
-  int win_cap;    // its size in bytes
-  // A window staged for a whole coding block (me_stage_cb_window): the searches of a reference's HOR / VER / QUAD partitions all start from
-  // the same centre, so one (CB + 2R)^2 window serves all eight of them.  cwin_ax / cwin_ay: absolute luma position of its first sample.
-  int cwin_valid, cwin_ref, cwin_ax, cwin_ay, cwin_Ww, cwin_Wh, cwin_pitch;
-};
-TK_DEV int mv_len1(int a) {
-  // (selects on values computed up front: as early returns this compiled to four nested exec-masked branches per vector component and candidate)
-  a = iabs(a);
-  const int big = 10 + ((a - 36) >> 4) + 1;   // a >= 36
-  const int mid = 5 + ((a - 4) >> 3) + 1;     // 4 <= a < 36
-  int r = a < 36 ? mid : big;
-  r = a < 4 ? 5 : r;
-  r = a < 2 ? 4 : r;
-  r = a < 1 ? 2 : r;
-  return r;
-}
-TK_DEV int quote_mv_bits(int dy, int dx) { return mv_len1(dx) + mv_len1(dy); }
-TK_DEV unsigned mv_cost(double lam, int dy, int dx) {
-  return (unsigned)mul_add_nofma(lam, (double)quote_mv_bits(dy, dx), 0.5);
-}
-// add_mvcandidate (encode_block.c:69-82) - call from ONE lane.
-TK_DEV void add_mvcand(MeWs* w_, int r, mv_t mv) {
-  const auto w = ldsc(lds_ld(&w_->lists));
-  mv_t imv = mk_mv((mv.x + 2) >> 2, (mv.y + 2) >> 2);
-  unsigned long long m = 1ull << ((((int)imv.y << 3) ^ (int)imv.x) & 63);
-  if (!(m & w->mvcand_mask[r])) {
-    const int n = w->mvcand_num[r];
-    w->mvcand[r][n].x = imv.x; w->mvcand[r][n].y = imv.y;
-    w->mvcand_num[r] = n + 1;
-  }
-  w->mvcand_mask[r] |= m;
-}
-
-// Evaluate n candidates and return min over (cost << 32 | index): the first candidate in evaluation
-// order among those with the smallest cost - exactly the winner of the reference's sequential
-// "if (cost < min) ..." scan.  prep(c) -> per-candidate context, item(ctx, r) -> partial SAD of work
-// item r < nit, cost(c, ctx, sad) -> cost.  G lanes share a candidate, partial sums are combined with
-// xor-shuffles, the final minimum with a 64-bit wave reduction; no LDS traffic, no barriers.
-template <class PrepF, class ItemF, class CostF>
-TK_DEV unsigned long long eval_min(const Team t, int n, int nit, PrepF prep, ItemF item, CostF cost) {
-  const int G = nit < t.size ? nit : t.size;
-  const int P = t.size / G;
-  const int slot = t.rank / G, sub = t.rank - slot * G;
-  unsigned long long best = ~0ull;
-  for (int c0 = 0; c0 < n; c0 += 2 * P) {
-    const int ca = c0 + slot, cb = c0 + P + slot;
-    const int va = ca < n, vb = cb < n;
-    auto xa = prep(va ? ca : 0);
-    auto xb = prep(vb ? cb : 0);
-    int la = 0, lb = 0;
-    if (va) for (int r = sub; r < nit; r += G) la += item(xa, r);
-    if (vb) for (int r = sub; r < nit; r += G) lb += item(xb, r);
-    la = team_group_sum(t, la, G); lb = team_group_sum(t, lb, G);
-    if (sub == 0) {
-      if (va) { unsigned long long k = ((unsigned long long)cost(ca, xa, la) << 32) | (unsigned)ca; best = k < best ? k : best; }
-      if (vb) { unsigned long long k = ((unsigned long long)cost(cb, xb, lb) << 32) | (unsigned)cb; best = k < best ? k : best; }
-    }
-  }
-  return TKU64(team_min64(t, best));
-}
-
-// Row segment of a block: up to 16 bytes (16 8-bit / 8 16-bit samples) held in four dwords, unused dwords zero.
-struct Seg16 { uint32_t d[4]; };
-#if !TK_HOST
-typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
-typedef u32x4 __attribute__((aligned(1), may_alias)) u32x4_unaligned;
-typedef u32x2 __attribute__((aligned(1), may_alias)) u32x2_unaligned;
-#endif
-// NB (4, 8 or 16) bytes at p.  SP: address space of p; LDS / scratch blocks are aligned to the segment size, frame planes
-// (global) may be read at any byte offset.
-template <int SP, int NB> TK_DEV Seg16 seg_load(const void* p) {
-  Seg16 r;
-  r.d[0] = r.d[1] = r.d[2] = r.d[3] = 0;
-#if TK_HOST
-  __builtin_memcpy(&r, p, (size_t)NB);
-#else
-  if constexpr (SP == SP_LDS) {
-    const auto q = (const TK_LDS uint8_t*)(uint32_t)(uintptr_t)p;
-    if constexpr (NB == 16) { const u32x4 v = *(const TK_LDS u32x4*)q; r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w; }
-    else if constexpr (NB == 8) { const u32x2 v = *(const TK_LDS u32x2*)q; r.d[0] = v.x; r.d[1] = v.y; }
-    else r.d[0] = *(const TK_LDS uint32_t*)q;
-  } else {
-    const auto q = (const TK_GLOBAL uint8_t*)p;
-    if constexpr (NB == 16) { const u32x4 v = *(const TK_GLOBAL u32x4_unaligned*)q; r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w; }
-    else if constexpr (NB == 8) { const u32x2 v = *(const TK_GLOBAL u32x2_unaligned*)q; r.d[0] = v.x; r.d[1] = v.y; }
-    else r.d[0] = *(const TK_GLOBAL u32_unaligned*)q;
-  }
-#endif
-  return r;
-}
-// sum of absolute sample differences of two NB-byte segments, added to acc
-template <typename PIX, int NB> TK_DEV int seg_sad(const Seg16& a, const Seg16& b, int acc) {
-#if TK_HOST
-  const PIX* x = (const PIX*)a.d;
-  const PIX* y = (const PIX*)b.d;
-  for (int k = 0; k < (int)(NB / sizeof(PIX)); k++) acc += iabs((int)x[k] - (int)y[k]);
-  return acc;
-#else
-  unsigned s = (unsigned)acc;
-  if constexpr (sizeof(PIX) == 1) { for (int k = 0; k < NB / 4; k++) s = __builtin_amdgcn_sad_u8(a.d[k], b.d[k], s); }    // 4 samples per lane-op
-  else { for (int k = 0; k < NB / 4; k++) s = __builtin_amdgcn_sad_u16(a.d[k], b.d[k], s); }                             // 2 samples per lane-op
-  return (int)s;
-#endif
-}
-
-// Truncating average (a + b) >> 1 per sample of two segments (bi-prediction, inter_prediction.c:228-247): per dword
-// (a & b) + (((a ^ b) >> 1) & M), M = every bit but each sample's top one.
-template <typename PIX> TK_DEV Seg16 seg_avg(const Seg16& a, const Seg16& b) {
-  const uint32_t M = sizeof(PIX) == 1 ? 0x7f7f7f7fu : 0x7fff7fffu;
-  Seg16 r;
-  for (int k = 0; k < 4; k++) r.d[k] = (a.d[k] & b.d[k]) + (((a.d[k] ^ b.d[k]) >> 1) & M);
-  return r;
-}
-// A candidate type with a second reference pointer `p2` is bi-predicted: its block is the truncating average of the blocks at p and p2
-// (same stride); such candidates always read the planes.
-template <class T, class = void> struct CandHasP2 { enum { value = 0 }; };
-template <class T> struct CandHasP2<T, decltype((void)((T*)nullptr)->p2)> { enum { value = 1 }; };
-
-// LDS search window of one motion search: the (w + 2R) x (h + 2R) samples of the reference plane around the search centre, staged
-// once per search with coalesced 16-byte row loads; the telescope, candidate-list, 5-offset, hexagon and sub-pel passes whose
-// blocks lie inside read it with aligned ds_read + v_alignbyte instead of gathering from the vector L1 (one coalesced global
-// round trip per search instead of one gather round trip per pass; profiles/r03_ubench_l1gather.log).  Samples of 1 or 2 bytes;
-// the reach R is the largest multiple of 4 up to kMeWinR for which the window fits the wave's LDS budget (MeWs::win_cap), at
-// least kMeWinRmin - otherwise the search reads the plane.  Row pitch = row bytes + 4: consecutive rows start in different banks.
-// Origin (ox, oy) is relative to the PU's co-located position in the reference plane.  The window lives in the wave's transform
-// workspace (idle during a search) and the bytes that follow it (SmallWs::win_extra).
-struct MeWin {
-  const uint32_t* w32;
-  int ox, oy, Ww, Wh;   // samples
-  int pitch;            // bytes
-  int on;
-};
-enum { kMeWinR = 20, kMeWinRmin = 8 };
-TK_DEV int me_win_bytes(int w, int h, int R, int S) { return ((w + 2 * R) * S + 4) * (h + 2 * R) + 4; }
-// NB bytes at byte offset `off` of the window (any alignment): NB/4 + 1 aligned dwords, funnel-shifted
-template <int NB> TK_DEV Seg16 win_seg(const uint32_t* w32, int off) {
-  Seg16 r;
-  r.d[0] = r.d[1] = r.d[2] = r.d[3] = 0;
-  const int d = off >> 2;
-  const unsigned sh = (unsigned)(off & 3);
-  uint32_t a[NB / 4 + 1];
-#if TK_HOST
-  for (int k = 0; k <= NB / 4; k++) a[k] = w32[d + k];
-  for (int k = 0; k < NB / 4; k++) r.d[k] = (uint32_t)((((unsigned long long)a[k + 1] << 32) | a[k]) >> (8 * sh));
-#else
-  const TK_LDS uint32_t* l = (const TK_LDS uint32_t*)(uint32_t)(uintptr_t)w32 + d;
-#pragma unroll
-  for (int k = 0; k <= NB / 4; k++) a[k] = l[k];
-#pragma unroll
-  for (int k = 0; k < NB / 4; k++) r.d[k] = __builtin_amdgcn_alignbyte(a[k + 1], a[k], sh);
-#endif
-  return r;
-}
-
-// Core of the full-pel passes: SAD of the org block against n candidate blocks; sink(c, x, sad, mine) is called in every lane
-// for every evaluated candidate slot (mine = this lane reports candidate c: first lane of its group, c < n).
-// Work item = one row segment of a candidate block (up to 16 bytes: ONE memory instruction per lane instead of one per four
-// samples).  PUs of up to `team size` segments (8-bit: everything up to 32x32): one segment per lane and candidate,
-// G = segments-per-candidate lanes form a group, team/G candidates are evaluated side by side and up to four such candidate
-// sets are in flight per lane; the group sum is a DPP butterfly.  Larger PUs: the whole team works on one candidate, four
-// segments per lane in flight.  cand(c) -> {clipped mv, displacement (dx, dy), pointer to the displaced reference block}.
-// An iteration whose candidate blocks all lie inside the staged window reads LDS, otherwise the reference plane.
-// One iteration of the small-PU path: U candidate sets (U * P candidates) starting at candidate c0.  Straight-line code: the
-// U reference segments are fetched back to back (window or plane, decided once for all of them) before the first SAD; slots
-// beyond n evaluate candidate 0 and are masked out in the sink.
-template <int SP, typename PIX, int NB, int U, class CandF, class SinkF>
-TK_DEV void seg_sads_iter(const Team t, int n, int c0, int P, int G, int slot, int sub, const Seg16& o, int roff, int woff, int width, int height,
-                          const MeWin& win, CandF cand, SinkF sink) {
-  Seg16 r[U];
-  decltype(cand(0)) x[U];
-  int outside = 0;
-#if !TK_HOST
-#pragma unroll
-#endif
-  for (int u = 0; u < U; u++) {
-    const int c = c0 + u * P + slot;
-    x[u] = cand(c < n ? c : 0);
-    outside |= !(x[u].dx >= win.ox && x[u].dx + width <= win.ox + win.Ww && x[u].dy >= win.oy && x[u].dy + height <= win.oy + win.Wh);
-  }
-  enum { BI = CandHasP2<decltype(cand(0))>::value };
-  const int use_win = !BI && win.on && team_ballot(t, outside) == 0ull;
-  if (use_win) {
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int u = 0; u < U; u++) r[u] = win_seg<NB>(win.w32, mul24(x[u].dy, win.pitch) + x[u].dx * (int)sizeof(PIX) + woff);
-  } else {
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int u = 0; u < U; u++) r[u] = seg_load<SP_GLOBAL, NB>(x[u].p + roff);
-    if constexpr (BI) {
-#if !TK_HOST
-#pragma unroll
-#endif
-      for (int u = 0; u < U; u++) r[u] = seg_avg<PIX>(r[u], seg_load<SP_GLOBAL, NB>(x[u].p2 + roff));
-    }
-  }
-#if !TK_HOST
-#pragma unroll
-#endif
-  for (int u = 0; u < U; u++) {
-    const int c = c0 + u * P + slot;
-    const int sad = team_group_sum(t, seg_sad<PIX, NB>(o, r[u], 0), G);
-    sink(c, x[u], sad, c < n && sub == 0);
-  }
-}
-template <int SP, typename PIX, int NB, class CandF, class SinkF>
-TK_DEV void seg_sads_nb(const Team t, int n_, const PIX* org, int ostride, int rstride, int width, int height, const MeWin& win,
-                        CandF cand, SinkF sink) {
-  // wave-uniform scalars (function arguments arrive in vector registers: without this every branch below is exec-mask code)
-  const int n = TKU(n_), tsz = TKU(t.size);
-  const int lw = NB / (int)sizeof(PIX);              // samples per segment
-  const int lgr = TKU(ilog2((unsigned)(width / lw)));   // log2(segments per row)
-  const int nit = height << lgr;                       // segments per candidate
-  const int G = nit < tsz ? nit : tsz;                 // powers of two
-  const int lgG = TKU(ilog2((unsigned)G));
-  const int P = tsz >> lgG;
-  const int slot = t.rank >> lgG, sub = t.rank & (G - 1);
-  if (nit <= tsz) {
-    const int i = sub >> lgr, j = (sub & ((1 << lgr) - 1)) * lw;
-    // (24-bit multiplies throughout the passes: row / pitch products are small, and v_mul_lo_u32 runs at a quarter of the rate)
-    const Seg16 o = seg_load<SP, NB>(org + mul24(i, ostride) + j);
-    const int roff = mul24(i, rstride) + j;
-    const int woff = mul24(i - win.oy, win.pitch) + (j - win.ox) * (int)sizeof(PIX);   // bytes
-    if (n <= P) seg_sads_iter<SP, PIX, NB, 1>(t, n, 0, P, G, slot, sub, o, roff, woff, width, height, win, cand, sink);
-    else if (n <= 2 * P) seg_sads_iter<SP, PIX, NB, 2>(t, n, 0, P, G, slot, sub, o, roff, woff, width, height, win, cand, sink);
-    else
-      for (int c0 = 0; c0 < n; c0 += 4 * P) seg_sads_iter<SP, PIX, NB, 4>(t, n, c0, P, G, slot, sub, o, roff, woff, width, height, win, cand, sink);
-  } else {
-    const int ipl = nit >> lgG;  // a multiple of 4 except on teams smaller than a wavefront (host simulation)
-    for (int c = 0; c < n; c++) {
-      const auto x = cand(c);
-      // the whole wave works on this candidate: one wave-uniform decision whether its block lies inside the staged window
-      const int use_win = TKU(!CandHasP2<decltype(cand(0))>::value && win.on && x.dx >= win.ox && x.dx + width <= win.ox + win.Ww && x.dy >= win.oy && x.dy + height <= win.oy + win.Wh);
-      const int wbase = mul24(x.dy - win.oy, win.pitch) + (x.dx - win.ox) * (int)sizeof(PIX);
-      int sad = 0;
-      for (int k0 = 0; k0 < ipl; k0 += 4) {
-        Seg16 o[4], r[4];
-#if !TK_HOST
-#pragma unroll
-#endif
-        for (int k = 0; k < 4; k++)
-          if (k0 + k < ipl) {
-            const int q = sub + (k0 + k) * G, i = q >> lgr, j = (q & ((1 << lgr) - 1)) * lw;
-            o[k] = seg_load<SP, NB>(org + mul24(i, ostride) + j);
-            if (use_win) r[k] = win_seg<NB>(win.w32, wbase + mul24(i, win.pitch) + j * (int)sizeof(PIX));
-            else r[k] = seg_load<SP_GLOBAL, NB>(x.p + mul24(i, rstride) + j);
-            if constexpr (CandHasP2<decltype(cand(0))>::value) r[k] = seg_avg<PIX>(r[k], seg_load<SP_GLOBAL, NB>(x.p2 + mul24(i, rstride) + j));
-          }
-#if !TK_HOST
-#pragma unroll
-#endif
-        for (int k = 0; k < 4; k++)
-          if (k0 + k < ipl) sad = seg_sad<PIX, NB>(o[k], r[k], sad);
-      }
-      sad = team_group_sum(t, sad, G);
-      sink(c, x, sad, sub == 0);
-    }
-  }
-}
-template <int SP, typename PIX, class CandF, class SinkF>
-TK_DEV void seg_sads(const Team t, int n, const PIX* org, int ostride, int rstride, int width, int height, const MeWin& win, CandF cand, SinkF sink) {
-  const int nb = (width < 16 / (int)sizeof(PIX) ? width : 16 / (int)sizeof(PIX)) * (int)sizeof(PIX);  // bytes per row segment
-  if (nb == 16) seg_sads_nb<SP, PIX, 16>(t, n, org, ostride, rstride, width, height, win, cand, sink);
-  else if (nb == 8) seg_sads_nb<SP, PIX, 8>(t, n, org, ostride, rstride, width, height, win, cand, sink);
-  else seg_sads_nb<SP, PIX, 4>(t, n, org, ostride, rstride, width, height, win, cand, sink);
-}
-// Full-pel candidate evaluation: min over the n candidates of (cost << 32 | index) - the first candidate in evaluation order
-// among those with the smallest cost, i.e. the winner of the reference's sequential strict-'<' scan.
-template <int SP, typename PIX, class CandF, class CostF>
-TK_DEV unsigned long long eval_fullpel(const Team t, int n, const PIX* org, int ostride, int rstride, int width, int height,
-                                       const MeWin& win, CandF cand, CostF cost) {
-  // Costs fit 24 bits - the SAD is at most 128 * 128 * 255 after the bit-depth shift, the vector cost at most sqrt(lambda) * 2 * mv_len1(65535) <
-  // 120 * 8208 - and n <= 64: the minimum over (cost << 8 | index) is ONE 32-bit wave reduction (4 DPP v_min + 4 v_readlane) instead of a 64-bit
-  // one; the host simulation asserts the bound.
-  unsigned best32 = ~0u;
-  seg_sads<SP>(t, n, org, ostride, rstride, width, height, win, cand, [&](int c, const decltype(cand(0))& x, int sad, int mine) {
-    const unsigned cst = cost(x, sad);
-#if TK_HOST
-    if (mine && ((cst >> 24) != 0u || c > 255)) { fprintf(stderr, "eval_fullpel: cost %u / index %d does not fit the packed key\n", cst, c); abort(); }
-#endif
-    unsigned k32 = (cst << 8) | (unsigned)c;
-    if (!mine) k32 = ~0u;
-    best32 = k32 < best32 ? k32 : best32;
-  });
-  const unsigned m = team_min32(t, best32);
-  return m == ~0u ? ~0ull : (((unsigned long long)(m >> 8)) << 32) | (m & 0xffu);
-}
-
-struct MeArgs {
-  int cb_size;           // `size` argument of motion_estimate = CB size
-  int ostride;           // stride of the original-sample block
-  int width, height;     // PU dims
-  int rstride;
-  int sign, fwidth, fheight, xpos, ypos;  // CB position (Appendix B.16)
-  int pu_x, pu_y;        // PU position (absolute, luma samples): only the LDS search window needs it
-  int enable_bipred, bitdepth;
-  int speed;             // encoder_speed (0 slow .. 2 fast)
-  double lam;            // sqrt(lambda)
-};
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Full-pel search of an 8-bit PU of up to 32x32 samples with ONE LANE PER CANDIDATE (round 5).
-// tools/ubench_me.cpp: with nothing else on the CU a search of a 4x4 PU costs the generic passes of motion_estimate 21 k cycles (4.3 k
-// per telescope step, 22 k per step for 32x32).  A pass there is ~450 wave-instructions at ~5 cycles each, and most of them are not sample
-// work: the lanes of a candidate GROUP (one row segment per lane) all form the candidate's vector, clip it, price it (two vector-bit
-// counts + a double-precision multiply-add: ~45 instructions) - and a lane does that for every candidate SET of the pass (4 per lane for
-// an 8x8 PU, 24 for a 32x32 one).  A wavefront issues one vector instruction per 4 clocks whatever the lanes do, so the instruction
-// count per lane is the time.  Here lane c IS candidate c of the pass (25 grid points, <= 64 list entries, 6 hexagon points): it forms,
-// clips and prices its vector ONCE and walks the rows of the block itself - per 16-byte row segment one broadcast read of the original
-// (same address in every lane), one unaligned read of its own displaced segment from the staged window (or the plane) and v_sad_u8.
-// 8x8: ~130 instructions per pass instead of ~450; 32x32: ~900 instead of ~5 000.  No cross-lane work except the final minimum.
-// Same passes, same order, same costs, winner = min over (cost, evaluation index) = the reference's sequential strict-'<' scan
-// (enc/encode_block.c:517-616); no duplicate-candidate bookkeeping (a vector evaluated twice cannot win twice).
-//   NB: bytes per row segment (4, 8: the PU width; 16: widths 16 and 32 = one or two segments per row)
-//   Round 6: PIX = uint16_t too (the reference's _hbd searches: SAD >> (bitdepth - 8), enc/encode_block.c:417-428): the same walk with v_sad_u16 on
-//   16-byte segments of eight samples - one (8 wide), two (16) or four (32) segments per row, `sh` = bitdepth - 8.
-template <typename PIX, int NB, int SP>
-TK_DEVNI unsigned long long me_cand_fullpel(const Team t, MeWs* w_, const PIX* org_, const PIX* ref, int a_cb, int a_ostride, int a_width, int a_height,
-                                            int a_rstride, int a_sign, int a_fw, int a_fh, int a_xpos, int a_ypos, double a_lam, const uint32_t* win_w32, int win_ox,
-                                            int win_oy, int win_Ww, int win_Wh, int win_pitch, int win_on, mv_t mvc, mv_t mvp, int ref_idx, int a_sh) {
-  constexpr int S = (int)sizeof(PIX), SPS = 16 / S;   // bytes per sample, samples per 16-byte segment
-  const int sh = tk_uniform(a_sh);
-  // (scalars one by one and the result in registers: a struct - by reference or by value - is a trip through the caller's stack in scratch memory)
-  struct { int cb_size, ostride, width, height, rstride, sign, fwidth, fheight, xpos, ypos; double lam; } a_in = {a_cb, a_ostride, a_width, a_height, a_rstride, a_sign, a_fw, a_fh, a_xpos, a_ypos, a_lam};
-  MeWin win_in;
-  win_in.w32 = win_w32; win_in.ox = win_ox; win_in.oy = win_oy; win_in.Ww = win_Ww; win_in.Wh = win_Wh; win_in.pitch = win_pitch; win_in.on = win_on;
-  const auto lists = ldsc(lds_ld(&w_->lists));
-  // wave-uniform scalars
-  const int cb = tk_uniform(a_in.cb_size), ostride = tk_uniform(a_in.ostride), width = tk_uniform(a_in.width), height = tk_uniform(a_in.height);
-  const int rstride = tk_uniform(a_in.rstride), sign = tk_uniform(a_in.sign), fw = tk_uniform(a_in.fwidth), fh = tk_uniform(a_in.fheight);
-  const int xpos = tk_uniform(a_in.xpos), ypos = tk_uniform(a_in.ypos);
-  const double lam = tk_uniform_f64(a_in.lam);
-  MeWin win;
-  win.w32 = tk_uniform_ptr(win_in.w32); win.ox = tk_uniform(win_in.ox); win.oy = tk_uniform(win_in.oy); win.Ww = tk_uniform(win_in.Ww);
-  win.Wh = tk_uniform(win_in.Wh); win.pitch = tk_uniform(win_in.pitch); win.on = tk_uniform(win_in.on);
-  mvc = mk_mv(tk_uniform(mvc.x), tk_uniform(mvc.y));
-  mvp = mk_mv(tk_uniform(mvp.x), tk_uniform(mvp.y));
-  ref_idx = tk_uniform(ref_idx);
-  org_ = tk_uniform_ptr(org_);
-  ref = tk_uniform_ptr(ref);
-  const int s = sign ? -1 : 1;
-  const int spr = NB == 16 ? ((width * S) >> 4) : 1;   // 16-byte segments per row
-  unsigned min_sad = kCostInit;
-  mv_t mv_opt = mk_mv(0, 0);
-  mv_t mv_ref = mk_mv(((mvc.x + 2) >> 2) << 2, ((mvc.y + 2) >> 2) << 2);
-  auto clip_free = [&](mv_t ctr, int R) -> int {   // motion_estimate's test: no vector within +-R quarter-pels of ctr needs clipping
-    const int ext = kPadY - 16, cy = s * ctr.y, cx = s * ctr.x;
-    return ypos + ((cy - R) >> 2) >= -ext && ypos + ((cy + R + 3) >> 2) + cb <= fh + ext && xpos + ((cx - R) >> 2) >= -ext && xpos + ((cx + R + 3) >> 2) + cb <= fw + ext;
-  };
-  // SAD of the block displaced by (dx + off, dy) against the original: the lane's own walk over the rows, four rows in flight (heights are
-  // multiples of four); window / plane and one / two segments per row are decided outside the loop (straight-line bodies: all eight or
-  // sixteen reads of an iteration are issued before the first SAD waits for them)
-  auto rows_sad = [&](auto win_tag, auto spr_tag, int dx, int dy, int off) -> unsigned {
-    constexpr int WIN = decltype(win_tag)::value, SPR = decltype(spr_tag)::value, ROWS = SPR >= 4 ? 1 : 4 / SPR;   // four segments in flight
-    unsigned sad = 0;
-    int wb = mul24(dy - win.oy, win.pitch) + (dx + off - win.ox) * S;   // bytes
-    const PIX* gb = ref + mul24(dy, rstride) + (dx + off);
-    const PIX* ob = org_;
-    for (int i = 0; i < height; i += ROWS) {
-      Seg16 o[ROWS * SPR], r[ROWS * SPR];
-#if !TK_HOST
-#pragma unroll
-#endif
-      for (int k = 0; k < ROWS; k++)
-#if !TK_HOST
-#pragma unroll
-#endif
-        for (int sg = 0; sg < SPR; sg++) {
-          o[k * SPR + sg] = seg_load<SP, NB>(ob + mul24(k, ostride) + SPS * sg);   // the same address in every lane
-          if constexpr (WIN) r[k * SPR + sg] = win_seg<NB>(win.w32, wb + mul24(k, win.pitch) + 16 * sg);
-          else r[k * SPR + sg] = seg_load<SP_GLOBAL, NB>(gb + mul24(k, rstride) + SPS * sg);
-        }
-#if !TK_HOST
-#pragma unroll
-#endif
-      for (int q = 0; q < ROWS * SPR; q++) sad = (unsigned)seg_sad<PIX, NB>(o[q], r[q], (int)sad);
-      wb += ROWS * win.pitch; gb += ROWS * rstride; ob += ROWS * ostride;
-    }
-    return sad;
-  };
-  struct T0 { enum { value = 0 }; };
-  struct T1 { enum { value = 1 }; };
-  struct T2 { enum { value = 2 }; };
-  struct T4 { enum { value = 4 }; };
-  auto block_sad = [&](int use_win, int dx, int dy, int off) -> unsigned {
-    if constexpr (NB == 16) {
-      if (spr == 2) return use_win ? rows_sad(T1(), T2(), dx, dy, off) : rows_sad(T0(), T2(), dx, dy, off);
-      if constexpr (S == 2) { if (spr == 4) return use_win ? rows_sad(T1(), T4(), dx, dy, off) : rows_sad(T0(), T4(), dx, dy, off); }
-    }
-    return use_win ? rows_sad(T1(), T1(), dx, dy, off) : rows_sad(T0(), T1(), dx, dy, off);
-  };
-  // Cost of THIS LANE's candidate (vector m, not yet clipped; `valid` lanes only - the others return ~0u).  Every vector is clipped with clip_mv,
-  // which leaves a vector inside the clip-free area alone: the same vectors motion_estimate evaluates with or without its `noclip` short cut.
-  // WIDE (16x16 coding blocks, candidate list): the cost is that of the best x offset of {-3, -1, 0, 1, 3} (first minimum) with the vector moved
-  // there (encode_block.c:430-453); *osel = that offset's index.
-  auto lane_cost = [&](mv_t m, int valid, auto wide_tag, unsigned* osel) -> unsigned {
-    constexpr int WIDE = decltype(wide_tag)::value;
-    m = clip_mv(m, ypos, xpos, fw, fh, cb, cb, sign);
-    {  // lanes without a candidate evaluate lane 0's vector (always a candidate) and drop the result: their own may point outside the staged window
-      const int mp0 = team_bcast0(t, (int)(uint16_t)m.x | ((int)m.y << 16));
-      if (!valid) m = mk_mv((int16_t)(mp0 & 0xffff), mp0 >> 16);
-    }
-    const int dx = s * (m.x >> 2), dy = s * (m.y >> 2);
-    const int x0 = dx - (WIDE ? 3 : 0), x1 = dx + (WIDE ? 3 : 0);
-    const int outside = valid && !(x0 >= win.ox && x1 + width <= win.ox + win.Ww && dy >= win.oy && dy + height <= win.oy + win.Wh);
-    const int use_win = win.on && team_ballot(t, outside) == 0ull;
-    unsigned sad;
-    int mx = m.x;
-    if constexpr (WIDE) {
-      sad = 1u << 31;
-      int bx = 0;
-      for (int q = 0; q < 5; q++) {
-        const int off = q == 0 ? -3 : q == 1 ? -1 : q == 2 ? 0 : q == 3 ? 1 : 3;
-        const unsigned v = block_sad(use_win, dx, dy, off);
-        if (v < sad) { sad = v; bx = off; *osel = (unsigned)q; }
-      }
-      mx = (int16_t)(m.x + ((s * bx) << 2));
-    } else
-      sad = block_sad(use_win, dx, dy, 0);
-    const unsigned cost = (sad >> sh) + mv_cost(lam, m.y - mvp.y, mx - mvp.x);
-    return valid ? cost : ~0u;
-  };
-  // min over the lanes [lo, lo + n) of (cost << 8 | lane - lo): the first candidate in evaluation order among the cheapest; ~0u for n == 0
-  auto range_min = [&](unsigned cost, int lo, int n) -> unsigned {
-    const int c = t.rank - lo;
-    unsigned k = (cost << 8) | (unsigned)(c & 0xff);
-    if (c < 0 || c >= n || cost == ~0u) k = ~0u;
-    return team_min32(t, k);
-  };
-  struct NoWide { enum { value = 0 }; };
-  struct Wide { enum { value = 1 }; };
-  auto grid_mv = [&](mv_t centre, int step, int c) -> mv_t {   // point c of the 5x5 grid of spacing `step` around centre; the centre is skipped after the first step
-    const int idx = (step < 32 && c >= 12) ? c + 1 : c;
-    const int q = mul24(idx, 13) >> 6;   // idx / 5
-    return mk_mv(centre.x + mul24(idx - q - (q << 2) - 2, step), centre.y + mul24(q - 2, step));
-  };
-  auto take = [&](mv_t m) {   // new optimum (clipped the way its candidate was), wave-uniform
-    m = clip_mv(m, ypos, xpos, fw, fh, cb, cb, sign);
-    mv_opt = mk_mv(tk_uniform(m.x), tk_uniform(m.y));
-  };
-  // --- telescope (encode_block.c:529-561): steps of 32, 16, 8, 4 quarter-pels.  A step is evaluated TOGETHER with the next one around the same
-  // centre (25 + 24 or 24 + 24 lanes): when the step leaves the optimum on its centre - the usual case with a good predictor - the next step's grid is
-  // exactly that one and its costs are already there; otherwise they are dropped and the next step runs from its real centre.
-  for (int step = 32; step >= 4;) {
-#ifdef TK_ME_NOSPEC   // tools/ubench_me.cpp: every step / round a pass of its own
-    const int n1 = step < 32 ? 24 : 25, n2 = 0;
-#else
-    const int n1 = step < 32 ? 24 : 25, n2 = step > 4 ? 24 : 0;
-#endif
-    const mv_t centre = mv_ref;
-    const int c1 = t.rank, c2 = t.rank - n1;
-    const int v1 = c1 < n1, v2 = c2 >= 0 && c2 < n2;
-    const mv_t m = v2 ? grid_mv(centre, step >> 1, c2) : grid_mv(centre, step, v1 ? c1 : 0);
-    const unsigned cost = lane_cost(m, v1 || v2, NoWide(), nullptr);
-    const unsigned k1 = range_min(cost, 0, n1);
-    if (k1 != ~0u && (k1 >> 8) < min_sad) { min_sad = k1 >> 8; take(grid_mv(centre, step, (int)(k1 & 0xffu))); }
-    mv_ref = mv_opt;
-    step >>= 1;
-    if (n2 && mv_ref.x == centre.x && mv_ref.y == centre.y) {   // the next step's centre is this one's: its costs are in lanes n1 .. n1 + 23
-      const unsigned k2 = range_min(cost, n1, n2);
-      if (k2 != ~0u && (k2 >> 8) < min_sad) { min_sad = k2 >> 8; take(grid_mv(centre, step, (int)(k2 & 0xffu))); }
-      mv_ref = mv_opt;
-      step >>= 1;
-    }
-  }
-  // --- candidate list (encode_block.c:564-581)
-  {
-    const int n = TKU(lists->mvcand_num[ref_idx]);
-    if (n > 0) {
-      auto list_mv = [&](int c) -> mv_t { return mk_mv((int16_t)(lists->mvcand[ref_idx][c].x << 2), (int16_t)(lists->mvcand[ref_idx][c].y << 2)); };
-      const int valid = t.rank < n;
-      const mv_t m = list_mv(valid ? t.rank : 0);
-      if (cb == 16) {
-        unsigned osel = 0;
-        const unsigned cost = lane_cost(m, valid, Wide(), &osel);
-        const unsigned k = range_min(cost, 0, n);
-        if (k != ~0u && (k >> 8) < min_sad) {
-          min_sad = k >> 8;
-          const int c = (int)(k & 0xffu);
-          const int q = team_read_lane(t, (int)osel, c);   // the winner's offset
-          mv_t mm = clip_mv(list_mv(c), ypos, xpos, fw, fh, cb, cb, sign);
-          const int bx = q == 0 ? -3 : q == 1 ? -1 : q == 2 ? 0 : q == 3 ? 1 : 3;
-          mm.x = (int16_t)(mm.x + ((s * bx) << 2));
-          mv_opt = mk_mv(tk_uniform(mm.x), tk_uniform(mm.y));   // (the moved vector is not clipped again: encode_block.c:447-451)
-        }
-      } else {
-        const unsigned cost = lane_cost(m, valid, NoWide(), nullptr);
-        const unsigned k = range_min(cost, 0, n);
-        if (k != ~0u && (k >> 8) < min_sad) { min_sad = k >> 8; take(list_mv((int)(k & 0xffu))); }
-      }
-    }
-    mv_ref = mv_opt;
-  }
-  // --- hexagon refinement (encode_block.c:583-616): up to 5 rounds of 6, then 3 points.  A round is evaluated together with the next round of
-  // every direction it can move in (6 + 6 x 3 or 3 + 3 x 3 lanes): the usual search ends after one or two rounds = one pass.
-  {
-    auto hex_off = [&](int dir, int* ox, int* oy) {
-      *ox = dir == 0 ? 1 : dir == 1 ? 2 : dir == 2 ? 1 : dir == 3 ? -1 : dir == 4 ? -2 : -1;
-      *oy = dir == 0 ? -1 : dir == 1 ? 0 : dir == 2 ? 1 : dir == 3 ? 1 : dir == 4 ? 0 : -1;
-    };
-    int start = 0, end = 5;
-    for (int round = 1; round < 6;) {
-      const int n = (end - start + 6) % 6 + 1;   // 6 in the first round, 3 afterwards
-      const mv_t centre = mv_ref;
-      // lanes [0, n): this round; lanes [n + 3 j, n + 3 j + 3): the next round if this one moves to its point j (new start = that direction - 1)
-      const int L = t.rank;
-      int ox, oy, valid = L < n * 4;
-      mv_t m;
-      {
-        const int j = L < n ? L : mul24(L - n, 11) >> 5;   // (L - n) / 3 for L - n < 32
-        const int dir1 = (start + (j < n ? j : 0)) % 6;
-        hex_off(dir1, &ox, &oy);
-        m = mk_mv(centre.x + ox * 4, centre.y + oy * 4);
-        if (L >= n) {
-          const int st2 = dir1 ? dir1 - 1 : 5;
-          const int dir2 = (st2 + (L - n - mul24(j, 3))) % 6;
-          hex_off(dir2, &ox, &oy);
-          m = mk_mv(m.x + ox * 4, m.y + oy * 4);
-        }
-      }
-#ifdef TK_ME_NOSPEC
-      const int speculate = 0;
-#else
-      const int speculate = round < 5;
-#endif
-      if (!speculate) valid = L < n;
-      const unsigned cost = lane_cost(m, valid, NoWide(), nullptr);
-      int which = -1;
-      const unsigned k = range_min(cost, 0, n);
-      auto hex_mv = [&](mv_t ctr, int st, int c) -> mv_t { int x, y; hex_off((st + c) % 6, &x, &y); return mk_mv(ctr.x + x * 4, ctr.y + y * 4); };
-      if (k != ~0u && (k >> 8) < min_sad) { min_sad = k >> 8; which = (int)(k & 0xffu); take(hex_mv(centre, start, which)); }
-      int best_dir = which < 0 ? -1 : (start + which) % 6;
-      // (the next round's centre is the point as this round evaluated it; a clipped point is not the speculated centre: fall back to a fresh pass)
-      const mv_t raw = which < 0 ? centre : hex_mv(centre, start, which);
-      mv_ref = mv_opt;
-      const int start0 = start;
-      start = best_dir ? best_dir - 1 : 5;
-      end = start + 2;
-      end -= (end >= 6) * 6;
-      round++;
-      if (best_dir < 0) break;
-      if (speculate && round < 6 && raw.x == mv_ref.x && raw.y == mv_ref.y) {
-        // the next round around the new centre: its three points are lanes n + 3 * which ..
-        (void)start0;
-        const mv_t centre2 = mv_ref;
-        const unsigned k2 = range_min(cost, n + 3 * which, 3);
-        int which2 = -1;
-        if (k2 != ~0u && (k2 >> 8) < min_sad) { min_sad = k2 >> 8; which2 = (int)(k2 & 0xffu); take(hex_mv(centre2, start, which2)); }
-        best_dir = which2 < 0 ? -1 : (start + which2) % 6;
-        mv_ref = mv_opt;
-        start = best_dir ? best_dir - 1 : 5;
-        end = start + 2;
-        end -= (end >= 6) * 6;
-        round++;
-        if (best_dir < 0) break;
-      }
-    }
-  }
-  return ((unsigned long long)min_sad << 32) | ((unsigned long long)(uint16_t)mv_opt.x << 16) | (unsigned long long)(uint16_t)mv_opt.y;
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// One sub-pel pass (the eight half- or quarter-pel neighbours of `base`, encode_block.c:628-663) of an 8-bit PU of up to 32x32 samples with
-// EIGHT LANES PER CANDIDATE (round 5).  tools/ubench_me.cpp: the generic pass costs ~8.5 k cycles for a 4x4 or 8x8 PU - nine luma_setups,
-// eight tap tables and eight vector prices formed by every lane (~900 wave-instructions) around ~200 instructions of sample work.  Here lane
-// (c, p) = candidate c = lane / 8, part p = lane % 8: a lane sets up, interpolates and prices ITS candidate only.  The PU is cut into
-// column strips of 8 (4 for 4-row PUs) samples; a strip needs the 13 (9) window rows around it once: per row two v_dot4 on the eight
-// bytes as loaded give the horizontal sum, six 24-bit multiply-adds per sample the vertical one (the strip form of subk8_strip_dy).
-// The (1/2, 1/2) position's 12-tap filter (inter_prediction.c:146-160) is the same machinery with two horizontal tap sets (rows 1, 4:
-// {0,0,1,1,0,0}; rows 2, 3: {0,1,2,2,1,0}), vertical weights {0,1,1,1,1,0} and rounding (sum + 8) >> 4, so the lanes of different
-// candidates do not diverge; the second tap set is only formed when some candidate of the pass is such a position (wave-uniform).
-// Requires every candidate's interpolation window inside the staged LDS window; returns 0xffffffff (the caller runs the generic pass) otherwise,
-// else min over the candidates of (cost << 8 | c), cost exactly motion_estimate's.
-template <int SP>
-TK_DEVNI unsigned me_cand8_subpel(const Team t, const uint8_t* org_, int a_ostride, int a_width, int a_height, int a_sign, int a_fw, int a_fh, int a_xpos, int a_ypos,
-                                  int a_bipred, double a_lam, const uint32_t* win_w32, int win_ox, int win_oy, int win_Ww, int win_Wh, int win_pitch, int win_on, mv_t base,
-                                  int d, mv_t mvp) {
-  enum : unsigned { kNone = 0xffffffffu };   // "not in the window": the caller runs the generic pass (a real key is below it: costs fit 24 bits)
-  struct { int ostride, width, height, sign, fwidth, fheight, xpos, ypos, enable_bipred; double lam; } a_in = {a_ostride, a_width, a_height, a_sign, a_fw, a_fh, a_xpos, a_ypos, a_bipred, a_lam};
-  MeWin win_in;
-  win_in.w32 = win_w32; win_in.ox = win_ox; win_in.oy = win_oy; win_in.Ww = win_Ww; win_in.Wh = win_Wh; win_in.pitch = win_pitch; win_in.on = win_on;
-  const int ostride = tk_uniform(a_in.ostride), width = tk_uniform(a_in.width), height = tk_uniform(a_in.height), sign = tk_uniform(a_in.sign);
-  const int fw = tk_uniform(a_in.fwidth), fh = tk_uniform(a_in.fheight), xpos = tk_uniform(a_in.xpos), ypos = tk_uniform(a_in.ypos);
-  const int bip = tk_uniform(a_in.enable_bipred);
-  const double lam = tk_uniform_f64(a_in.lam);
-  MeWin win;
-  win.w32 = tk_uniform_ptr(win_in.w32); win.ox = tk_uniform(win_in.ox); win.oy = tk_uniform(win_in.oy); win.Ww = tk_uniform(win_in.Ww);
-  win.Wh = tk_uniform(win_in.Wh); win.pitch = tk_uniform(win_in.pitch); win.on = tk_uniform(win_in.on);
-  base = mk_mv(tk_uniform(base.x), tk_uniform(base.y));
-  mvp = mk_mv(tk_uniform(mvp.x), tk_uniform(mvp.y));
-  d = tk_uniform(d);
-  org_ = tk_uniform_ptr(org_);
-  if (!win.on) return kNone;
-  const int c = t.rank >> 3, part = t.rank & 7;
-  // order: (0,-d) (-d,0) (d,0) (0,d) (-d,-d) (-d,d) (d,-d) (d,d) as (y,x)
-  const int oy = c == 0 ? 0 : c == 1 ? -d : c == 2 ? d : c == 3 ? 0 : c == 4 ? -d : c == 5 ? -d : d;
-  const int ox = c == 0 ? -d : c == 1 ? 0 : c == 2 ? 0 : c == 3 ? d : c == 4 ? -d : c == 5 ? d : c == 6 ? -d : d;
-  const mv_t mv = mk_mv(base.x + ox, base.y + oy);
-  const SubPel sp = luma_setup(mv, sign, width, height, fw, fh, xpos, ypos, bip);
-  const int centre = sp.ver_frac == 2 && sp.hor_frac == 2 && bip < 2;
-  // interpolation window of the whole PU for this candidate: rows ver_int - 2 .. ver_int + height + 2, columns hor_int - 2 .. hor_int + width + 5
-  const int outside = !(sp.hor_int - 2 >= win.ox && sp.hor_int + width + 6 <= win.ox + win.Ww && sp.ver_int - 2 >= win.oy && sp.ver_int + height + 3 <= win.oy + win.Wh);
-  if (team_ballot(t, outside) != 0ull) return kNone;
-  const int dual = team_ballot(t, centre) != 0ull;   // wave-uniform
-  // per-lane filter description (see the header): horizontal taps A (vertical positions 0, 1, 4, 5) and B (2, 3) as int8 lanes, vertical weights
-  const unsigned long long thA = centre ? 0x0000000001010000ull : sp.ph, thB = centre ? 0x0000000102020100ull : sp.ph;
-  const int biasA = centre ? 128 * 2 : 128 * 64, biasB = centre ? 128 * 6 : 128 * 64;
-  int tv[6];
-  for (int m = 0; m < 6; m++) tv[m] = centre ? (m >= 1 && m <= 4 ? 1 : 0) : sp.tv[m];
-  const int rnd = centre ? 8 : 2048, rsh = centre ? 4 : 12;
-  const int lgw = ilog2((unsigned)width);
-  const int SH = height == 4 ? 4 : 8;                      // strip height
-  const int units = width * (height == 4 ? 1 : (height >> 3));
-  unsigned sad = 0;
-  auto strip = [&](auto sh_tag, auto dual_tag, int i0, int j) {
-    constexpr int SHC = decltype(sh_tag)::value, DUAL = decltype(dual_tag)::value, NR = SHC + 5;
-    const int woff = mul24(i0 + sp.ver_int - 2 - win.oy, win.pitch) + (j + sp.hor_int - 2 - win.ox);
-    int hA[NR], hB[NR];
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int r = 0; r < NR; r++) {
-      const Seg16 sg = win_seg<8>(win.w32, woff + mul24(r, win.pitch));
-      const unsigned lo = sg.d[0] ^ 0x80808080u, hi = sg.d[1] ^ 0x80808080u;   // samples - 128 as int8 lanes
-      hA[r] = dot4_i8((int)(unsigned)thA, (int)lo, dot4_i8((int)(unsigned)(thA >> 32), (int)hi, biasA));
-      if constexpr (DUAL) hB[r] = dot4_i8((int)(unsigned)thB, (int)lo, dot4_i8((int)(unsigned)(thB >> 32), (int)hi, biasB));
-      else hB[r] = hA[r];
-    }
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int q = 0; q < SHC; q++) {
-      int sum = mul24(tv[0], hA[q]) + mul24(tv[1], hA[q + 1]) + mul24(tv[2], hB[q + 2]) + mul24(tv[3], hB[q + 3]) + mul24(tv[4], hA[q + 4]) + mul24(tv[5], hA[q + 5]);
-      const int pr = sat_pix((sum + rnd) >> rsh, 8);
-      const int o = (int)spc<SP>(org_)[mul24(i0 + q, ostride) + j];
-      sad += (unsigned)(o > pr ? o - pr : pr - o);
-    }
-  };
-  struct S4 { enum { value = 4 }; };
-  struct S8 { enum { value = 8 }; };
-  struct D0 { enum { value = 0 }; };
-  struct D1 { enum { value = 1 }; };
-  for (int u = part; u < units; u += 8) {
-    const int j = u & (width - 1), i0 = (u >> lgw) << 3;
-    if (SH == 4) { if (dual) strip(S4(), D1(), 0, j); else strip(S4(), D0(), 0, j); }
-    else { if (dual) strip(S8(), D1(), i0, j); else strip(S8(), D0(), i0, j); }
-  }
-  const unsigned tot = (unsigned)team_group_sum(t, (int)sad, 8);
-  const unsigned cost = tot + mv_cost(lam, mv.y - mvp.y, mv.x - mvp.x);
-  unsigned k = (cost << 8) | (unsigned)c;
-  if (part != 0) k = ~0u;
-  return team_min32(t, k);
-}
-
-
-// The same pass on 16-bit samples (round 6): lane (c, p) = candidate c = lane / 8, part p = lane % 8; a strip is one column of 8 (4) samples whose 13 (9)
-// window rows are read once - six samples = three dwords at the candidate's byte offset (win_seg: any alignment), the six horizontal taps packed in
-// pairs: three v_dot2_i32_i16 per row sum (|sum| <= 94 * 4095 < 2^19), six 24-bit multiply-adds per sample vertically; the (1/2, 1/2) position's 12-tap
-// filter as two horizontal tap sets with vertical weights {0,1,1,1,1,0} and (sum + 8) >> 4, exactly as in me_cand8_subpel.  SAD >> (bitdepth - 8).
-template <int SP>
-TK_DEVNI unsigned me_cand16_subpel(const Team t, const uint16_t* org_, int a_ostride, int a_width, int a_height, int a_sign, int a_fw, int a_fh, int a_xpos, int a_ypos,
-                                   int a_bipred, double a_lam, const uint32_t* win_w32, int win_ox, int win_oy, int win_Ww, int win_Wh, int win_pitch, int win_on, mv_t base,
-                                   int d, mv_t mvp, int a_bitdepth) {
-  enum : unsigned { kNone = 0xffffffffu };
-  struct { int ostride, width, height, sign, fwidth, fheight, xpos, ypos, enable_bipred, bitdepth; double lam; } a_in = {a_ostride, a_width, a_height, a_sign, a_fw, a_fh, a_xpos, a_ypos, a_bipred, a_bitdepth, a_lam};
-  MeWin win_in;
-  win_in.w32 = win_w32; win_in.ox = win_ox; win_in.oy = win_oy; win_in.Ww = win_Ww; win_in.Wh = win_Wh; win_in.pitch = win_pitch; win_in.on = win_on;
-  const int ostride = tk_uniform(a_in.ostride), width = tk_uniform(a_in.width), height = tk_uniform(a_in.height), sign = tk_uniform(a_in.sign);
-  const int fw = tk_uniform(a_in.fwidth), fh = tk_uniform(a_in.fheight), xpos = tk_uniform(a_in.xpos), ypos = tk_uniform(a_in.ypos);
-  const int bip = tk_uniform(a_in.enable_bipred), bitdepth = tk_uniform(a_in.bitdepth);
-  const double lam = tk_uniform_f64(a_in.lam);
-  MeWin win;
-  win.w32 = tk_uniform_ptr(win_in.w32); win.ox = tk_uniform(win_in.ox); win.oy = tk_uniform(win_in.oy); win.Ww = tk_uniform(win_in.Ww);
-  win.Wh = tk_uniform(win_in.Wh); win.pitch = tk_uniform(win_in.pitch); win.on = tk_uniform(win_in.on);
-  base = mk_mv(tk_uniform(base.x), tk_uniform(base.y));
-  mvp = mk_mv(tk_uniform(mvp.x), tk_uniform(mvp.y));
-  d = tk_uniform(d);
-  org_ = tk_uniform_ptr(org_);
-  if (!win.on) return kNone;
-  const int c = t.rank >> 3, part = t.rank & 7;
-  const int oy = c == 0 ? 0 : c == 1 ? -d : c == 2 ? d : c == 3 ? 0 : c == 4 ? -d : c == 5 ? -d : d;
-  const int ox = c == 0 ? -d : c == 1 ? 0 : c == 2 ? 0 : c == 3 ? d : c == 4 ? -d : c == 5 ? d : c == 6 ? -d : d;
-  const mv_t mv = mk_mv(base.x + ox, base.y + oy);
-  const SubPel sp = luma_setup(mv, sign, width, height, fw, fh, xpos, ypos, bip);
-  const int centre = sp.ver_frac == 2 && sp.hor_frac == 2 && bip < 2;
-  const int outside = !(sp.hor_int - 2 >= win.ox && sp.hor_int + width + 6 <= win.ox + win.Ww && sp.ver_int - 2 >= win.oy && sp.ver_int + height + 3 <= win.oy + win.Wh);
-  if (team_ballot(t, outside) != 0ull) return kNone;
-  const int dual = team_ballot(t, centre) != 0ull;   // wave-uniform
-  auto pair = [](int a, int b) -> uint32_t { return (uint32_t)(uint16_t)(int16_t)a | ((uint32_t)(uint16_t)(int16_t)b << 16); };
-  uint32_t tA[3], tB[3];
-  for (int q = 0; q < 3; q++) {
-    tA[q] = centre ? (q == 1 ? pair(1, 1) : 0u) : pair(sp.th[2 * q], sp.th[2 * q + 1]);                                        // rows 0, 1, 4, 5: {0,0,1,1,0,0}
-    tB[q] = centre ? (q == 0 ? pair(0, 1) : q == 1 ? pair(2, 2) : pair(1, 0)) : pair(sp.th[2 * q], sp.th[2 * q + 1]);         // rows 2, 3:       {0,1,2,2,1,0}
-  }
-  int tv[6];
-  for (int m = 0; m < 6; m++) tv[m] = centre ? (m >= 1 && m <= 4 ? 1 : 0) : sp.tv[m];
-  const int rnd = centre ? 8 : 2048, rsh = centre ? 4 : 12;
-  const int lgw = ilog2((unsigned)width);
-  const int SH = height == 4 ? 4 : 8;
-  const int units = width * (height == 4 ? 1 : (height >> 3));
-  unsigned sad = 0;
-  auto strip = [&](auto sh_tag, auto dual_tag, int i0, int j) {
-    constexpr int SHC = decltype(sh_tag)::value, DUAL = decltype(dual_tag)::value, NR = SHC + 5;
-    const int woff = mul24(i0 + sp.ver_int - 2 - win.oy, win.pitch) + ((j + sp.hor_int - 2 - win.ox) << 1);   // bytes
-    int hA[NR], hB[NR];
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int r = 0; r < NR; r++) {
-      const Seg16 sg = win_seg<12>(win.w32, woff + mul24(r, win.pitch));   // six samples
-      hA[r] = dot2_i16(tA[0], sg.d[0], dot2_i16(tA[1], sg.d[1], dot2_i16(tA[2], sg.d[2], 0)));
-      if constexpr (DUAL) hB[r] = dot2_i16(tB[0], sg.d[0], dot2_i16(tB[1], sg.d[1], dot2_i16(tB[2], sg.d[2], 0)));
-      else hB[r] = hA[r];
-    }
-#if !TK_HOST
-#pragma unroll
-#endif
-    for (int q = 0; q < SHC; q++) {
-      int sum = mul24(tv[0], hA[q]) + mul24(tv[1], hA[q + 1]) + mul24(tv[2], hB[q + 2]) + mul24(tv[3], hB[q + 3]) + mul24(tv[4], hA[q + 4]) + mul24(tv[5], hA[q + 5]);
-      const int pr = sat_pix((sum + rnd) >> rsh, bitdepth);
-      const int o = (int)spc<SP>(org_)[mul24(i0 + q, ostride) + j];
-      sad += (unsigned)(o > pr ? o - pr : pr - o);
-    }
-  };
-  struct S4 { enum { value = 4 }; };
-  struct S8 { enum { value = 8 }; };
-  struct D0 { enum { value = 0 }; };
-  struct D1 { enum { value = 1 }; };
-  for (int u = part; u < units; u += 8) {
-    const int j = u & (width - 1), i0 = (u >> lgw) << 3;
-    if (SH == 4) { if (dual) strip(S4(), D1(), 0, j); else strip(S4(), D0(), 0, j); }
-    else { if (dual) strip(S8(), D1(), i0, j); else strip(S8(), D0(), i0, j); }
-  }
-  const unsigned tot = (unsigned)team_group_sum(t, (int)sad, 8);
-  const unsigned cost = (tot >> (bitdepth - 8)) + mv_cost(lam, mv.y - mvp.y, mv.x - mvp.x);
-  unsigned k = (cost << 8) | (unsigned)c;
-  if (part != 0) k = ~0u;
-  return team_min32(t, k);
-}
-
-
-// Bilinear sub-pel approximations of encoder_speed > 0 (sad_calc_fasthalf enc/encode_block.c:174-283 ==
-// sad_calc_fasthalf_simd enc_kernels.c:330, sad_calc_fastquarter :286-415): the SADs of the 8 half-
-// (quarter-) pel neighbours of the centre built from rounding (avg) and truncating (rdavg) byte averages;
-// returns the smallest of them and its offset.  Lanes split the samples, 8 shuffle reductions.
-template <int SP, typename PIX> TK_DEV unsigned fast_halfpel(const Team t, const PIX* a_, const PIX* b, int as, int bs, int width, int height, int* bx, int* by) {
-  const auto a = spc<SP>(a_);
-  int tl = 0, tr = 0, br = 0, bl = 0, top = 0, right = 0, down = 0, left = 0;
-  const Pow2 dw = mk_pow2(width);
-  for (int r = t.rank; r < width * height; r += t.size) {
-    int i, j;
-    split2(dw, r, i, j);
-    const PIX* c = b + i * bs + j;
-    auto B = [&](int dy, int dx) -> int { return (int)c[dy * bs + dx]; };
-    auto av = [](int x, int y) { return (x + y + 1) >> 1; };
-    auto rd = [](int x, int y) { return (x + y) >> 1; };
-    const int o = (int)a[i * as + j];
-    const int h_l = av(B(0, -1), B(0, 0)), h_r = av(B(0, 0), B(0, 1));
-    const int v4 = av(B(-2, 0), B(1, 0));          // column j,   rows -2 / +1
-    const int v4b = av(B(-1, 0), B(2, 0));         // column j,   rows -1 / +2
-    const int t6 = av(B(0, -2), B(0, 1));          // row 0, cols -2 / +1
-    const int t7 = av(B(0, -1), B(0, 2));          // row 0, cols -1 / +2
-    const int ptl = rd(rd(rd(av(B(-2, -1), B(1, -1)), v4), rd(av(B(-1, -2), B(-1, 1)), t6)), rd(av(B(-1, -1), B(-1, 0)), h_l));
-    const int ptr = rd(rd(rd(v4, av(B(-2, 1), B(1, 1))), rd(t7, av(B(-1, -1), B(-1, 2)))), rd(av(B(-1, 0), B(-1, 1)), h_r));
-    const int pbl = rd(rd(rd(v4b, av(B(-1, -1), B(2, -1))), rd(t6, av(B(1, -2), B(1, 1)))), rd(av(B(1, -1), B(1, 0)), h_l));
-    const int pbr = rd(rd(rd(v4b, av(B(-1, 1), B(2, 1))), rd(t7, av(B(1, -1), B(1, 2)))), rd(h_r, av(B(1, 0), B(1, 1))));
-    left += iabs(o - h_l); right += iabs(o - h_r);
-    down += iabs(o - av(B(0, 0), B(1, 0))); top += iabs(o - av(B(0, 0), B(-1, 0)));
-    tl += iabs(o - ptl); tr += iabs(o - ptr); br += iabs(o - pbr); bl += iabs(o - pbl);
-  }
-  unsigned utop = (unsigned)team_sum(t, top), uright = (unsigned)team_sum(t, right), udown = (unsigned)team_sum(t, down), uleft = (unsigned)team_sum(t, left);
-  unsigned utl = (unsigned)team_sum(t, tl), utr = (unsigned)team_sum(t, tr), ubr = (unsigned)team_sum(t, br), ubl = (unsigned)team_sum(t, bl);
-  int x = 0, y = -2;
-  if (udown < utop) { y = 2; utop = udown; }
-  if (uright < utop) { x = 2; y = 0; utop = uright; }
-  if (uleft < utop) { x = -2; y = 0; utop = uleft; }
-  if (utl < utop) { x = -2; y = -2; utop = utl; }
-  if (utr < utop) { x = 2; y = -2; utop = utr; }
-  if (ubr < utop) { x = 2; y = 2; utop = ubr; }
-  if (ubl < utop) { x = -2; y = 2; utop = ubl; }
-  *bx = x; *by = y;
-  return utop;
-}
-
-template <int SP, typename PIX> TK_DEV unsigned fast_quarterpel(const Team t, const PIX* o__, const PIX* r_, int os, int rs, int width, int height, int* bx, int* by) {
-  const auto o_ = spc<SP>(o__);
-  int tl = 0, tr = 0, br = 0, bl = 0, top = 0, right = 0, down = 0, left = 0;
-  const int hx = *bx, hy = *by;  // half-pel offset chosen before (0 or +-2): selects the interpolation pattern
-  const Pow2 dw = mk_pow2(width);
-  for (int q = t.rank; q < width * height; q += t.size) {
-    int i, j;
-    split2(dw, q, i, j);
-    const PIX* c = r_ + i * rs + j;
-    auto av = [](int x, int y) { return (x + y + 1) >> 1; };
-    const int o = (int)o_[i * os + j];
-    const int a = c[0], d = c[1], f = c[rs];
-    int p_tl, p_top, p_tr, p_left, p_right, p_bl, p_down, p_br;
-    if (hx & hy) {
-      const int e = c[rs + 1];
-      const int ad = av(a, d), de = av(d, e), af = av(a, f), fe = av(f, e);
-      p_tl = (ad + af) >> 1; p_top = (de + a) >> 1; p_tr = (ad + de) >> 1; p_left = (ad + f) >> 1; p_right = (ad + e) >> 1;
-      p_bl = (af + fe) >> 1; p_down = (de + f) >> 1; p_br = (de + fe) >> 1;
-    } else if (hx) {
-      const int b = c[-rs], cc = c[-rs + 1], e = c[rs + 1];
-      const int ad = av(a, d), de = av(d, e), dc = av(d, cc), af = av(a, f), ab = av(a, b);
-      p_tl = (ad + ab) >> 1; p_top = (dc + a) >> 1; p_tr = (ad + dc) >> 1; p_left = (ad + a) >> 1; p_right = (ad + d) >> 1;
-      p_bl = (ad + af) >> 1; p_down = (af + d) >> 1; p_br = (ad + de) >> 1;
-    } else if (hy) {
-      const int e = c[rs + 1], g = c[rs - 1], h = c[-1];
-      const int ad = av(a, d), af = av(a, f), fe = av(f, e), ah = av(a, h), gf = av(g, f);
-      p_tl = (ah + af) >> 1; p_top = (af + a) >> 1; p_tr = (ad + af) >> 1; p_left = (gf + a) >> 1; p_right = (ad + f) >> 1;
-      p_bl = (af + gf) >> 1; p_down = (af + f) >> 1; p_br = (af + fe) >> 1;
-    } else {
-      const int b = c[-rs], h = c[-1];
-      const int ad = av(a, d), af = av(a, f), ah = av(a, h), ab = av(a, b);
-      p_tl = (ah + ab) >> 1; p_top = (ab + a) >> 1; p_tr = (ad + ab) >> 1; p_left = (ah + a) >> 1; p_right = (ad + a) >> 1;
-      p_bl = (ah + af) >> 1; p_down = (af + a) >> 1; p_br = (af + ad) >> 1;
-    }
-    tl += iabs(o - p_tl); top += iabs(o - p_top); tr += iabs(o - p_tr); left += iabs(o - p_left); right += iabs(o - p_right);
-    bl += iabs(o - p_bl); down += iabs(o - p_down); br += iabs(o - p_br);
-  }
-  unsigned utop = (unsigned)team_sum(t, top), uright = (unsigned)team_sum(t, right), udown = (unsigned)team_sum(t, down), uleft = (unsigned)team_sum(t, left);
-  unsigned utl = (unsigned)team_sum(t, tl), utr = (unsigned)team_sum(t, tr), ubr = (unsigned)team_sum(t, br), ubl = (unsigned)team_sum(t, bl);
-  int x = 0, y = -1;
-  if (utl < utop) { x = -1; utop = utl; }
-  if (utr < utop) { x = 1; utop = utr; }
-  if (uleft < utop) { x = -1; y = 0; utop = uleft; }
-  if (uright < utop) { x = 1; y = 0; utop = uright; }
-  if (ubl < utop) { x = -1; y = 1; utop = ubl; }
-  if (udown < utop) { x = 0; y = 1; utop = udown; }
-  if (ubr < utop) { x = 1; y = 1; utop = ubr; }
-  *bx = x; *by = y;
-  return utop;
-}
 
 // Stage ONE window for the coding block at (cb_x, cb_y) of size cb in reference `ref_idx` (ref_cb = its co-located sample in the padded
 // plane), centred on the rounded search centre mvc: the HOR / VER / QUAD searches of this reference (eight motion_estimate calls) all start
@@ -921,7 +67,7 @@ template <typename PIX, int SP>
 TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const PIX* ref, const MeArgs& a_in, mv_t mvc,
                                 mv_t mvp, int ref_idx, mv_t* mv_out) {
   TK_PROF_T0();
-#if defined(THOR_PROF_ME) && defined(THOR_PROF) && !TK_HOST
+#if TK_PROF_ME
   const long long pme0_ = (long long)__builtin_readcyclecounter();
 #endif
   const auto w = ldsc(w_);
@@ -929,16 +75,9 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
   const auto orgs = spc<SP>(org);
   auto cmv_get = [&](int c) -> mv_t { return mk_mv(w->cmv[c].x, w->cmv[c].y); };
   auto cmv_set = [&](int c, mv_t m) { w->cmv[c].x = m.x; w->cmv[c].y = m.y; };
-  MeArgs a_u;
-  a_u.cb_size = tk_uniform(a_in.cb_size); a_u.ostride = tk_uniform(a_in.ostride); a_u.width = tk_uniform(a_in.width);
-  a_u.height = tk_uniform(a_in.height); a_u.rstride = tk_uniform(a_in.rstride); a_u.sign = tk_uniform(a_in.sign);
-  a_u.fwidth = tk_uniform(a_in.fwidth); a_u.fheight = tk_uniform(a_in.fheight); a_u.xpos = tk_uniform(a_in.xpos);
-  a_u.ypos = tk_uniform(a_in.ypos); a_u.enable_bipred = tk_uniform(a_in.enable_bipred); a_u.bitdepth = tk_uniform(a_in.bitdepth);
-  a_u.speed = tk_uniform(a_in.speed); a_u.lam = tk_uniform_f64(a_in.lam);
-  a_u.pu_x = tk_uniform(a_in.pu_x); a_u.pu_y = tk_uniform(a_in.pu_y);
-  const MeArgs& a = a_u;
-  mvc = mk_mv(tk_uniform(mvc.x), tk_uniform(mvc.y));
-  mvp = mk_mv(tk_uniform(mvp.x), tk_uniform(mvp.y));
+  const MeArgs a = uniform(a_in);
+  mvc = uniform(mvc);
+  mvp = uniform(mvp);
   ref_idx = tk_uniform(ref_idx);
   const int s = a.sign ? -1 : 1;
   const int sh = a.bitdepth - 8;
@@ -969,7 +108,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
     x.rate = rate_of(x.mv);
     return x;
   };
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
   long long pq_ = (long long)__builtin_readcyclecounter();
   if (t.rank == 0) w->prof[11] += 1;
 #endif
@@ -1165,7 +304,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
     mv_ref = mv_opt;
   }
 
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
   if (t.rank == 0) w->prof[13] += (long long)__builtin_readcyclecounter() - pq_;
   pq_ = (long long)__builtin_readcyclecounter();
 #endif
@@ -1214,7 +353,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
     mv_ref = mv_opt;
   }
 
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
   if (t.rank == 0) w->prof[14] += (long long)__builtin_readcyclecounter() - pq_;
   pq_ = (long long)__builtin_readcyclecounter();
 #endif
@@ -1246,7 +385,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
     }
   }
 
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
   if (t.rank == 0) w->prof[15] += (long long)__builtin_readcyclecounter() - pq_;
 #endif
   }   // !small_done
@@ -1262,7 +401,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
 #endif
   TK_PROF_ADD(w, 2);
   // --- half-pel then quarter-pel (encode_block.c:628-663)
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
   pt0_ = (long long)__builtin_readcyclecounter();
 #endif
   unsigned cmin = min_sad;
@@ -1342,7 +481,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
     unsigned long long k;
     (void)0;
     TK_PROF_MARK(ps1_);
-#if defined(THOR_PROF_SUBPEL) && defined(THOR_PROF) && !TK_HOST   // tools/ubench_me.cpp: set-up / sample loop / reduction of a sub-pel pass
+#if TK_PROF_SUBPEL   // tools/ubench_me.cpp: set-up / sample loop / reduction of a sub-pel pass
     if (t.rank == 0) w->prof[6] += ps1_ - ps0_;
 #endif
     if (in_window) {
@@ -1368,24 +507,16 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
             unsigned long long wb[15];
             if (sub_in_win) {   // the rows come out of the staged window
               const int woff = (i0 + ctr.ver_int - 3 - win.oy) * win.pitch + (j + ctr.hor_int - 3 - win.ox);
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int q = 0; q < 15; q++) { const Seg16 sg = win_seg<8>(win.w32, woff + q * win.pitch); wb[q] = (((unsigned long long)sg.d[1] << 32) | sg.d[0]) ^ 0x8080808080808080ull; }
             } else {
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int q = 0; q < 15; q++) wb[q] = gload64(p0 + q * a.rstride) ^ 0x8080808080808080ull;
             }
             int o8[8];
-#if !TK_HOST
-#pragma unroll
-#endif
+            TK_UNROLL
             for (int q = 0; q < 8; q++) o8[q] = (int)orgs[(i0 + q) * a.ostride + j];
-#if !TK_HOST
-#pragma unroll
-#endif
+            TK_UNROLL
             for (int c = 0; c < 8; c++) sad8[c] = subk8_strip(wb, k8[c], o8, sad8[c]);
           }
         }
@@ -1408,25 +539,17 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
               uint32_t wb[15][4];
               if (sub_in_win) {
                 const int woff = (i0 + ctr.ver_int - 3 - win.oy) * win.pitch + (j + ctr.hor_int - 3 - win.ox) * 2;
-#if !TK_HOST
-#pragma unroll
-#endif
+                TK_UNROLL
                 for (int q = 0; q < 15; q++) { const Seg16 sg = win_seg<16>(win.w32, woff + q * win.pitch); wb[q][0] = sg.d[0]; wb[q][1] = sg.d[1]; wb[q][2] = sg.d[2]; wb[q][3] = sg.d[3]; }
               } else {
                 const PIX* p0 = ref + (i0 + ctr.ver_int - 3) * a.rstride + (j + ctr.hor_int - 3);
-#if !TK_HOST
-#pragma unroll
-#endif
+                TK_UNROLL
                 for (int q = 0; q < 15; q++) { const Seg16 sg = seg_load<SP_GLOBAL, 16>(p0 + q * a.rstride); wb[q][0] = sg.d[0]; wb[q][1] = sg.d[1]; wb[q][2] = sg.d[2]; wb[q][3] = sg.d[3]; }
               }
               int o8[8];
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int q = 0; q < 8; q++) o8[q] = (int)orgs[(i0 + q) * a.ostride + j];
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int c = 0; c < 8; c++) sad8[c] = subk16_strip(wb, k16[c], o8, sad8[c], a.bitdepth);
             }
           } else
@@ -1436,21 +559,15 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
             uint32_t rows[8][4];
             if (sub_in_win) {
               const int woff = (i + ctr.ver_int - 3 - win.oy) * win.pitch + (j + ctr.hor_int - 3 - win.ox) * 2;
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int q = 0; q < 8; q++) { const Seg16 sg = win_seg<16>(win.w32, woff + q * win.pitch); rows[q][0] = sg.d[0]; rows[q][1] = sg.d[1]; rows[q][2] = sg.d[2]; rows[q][3] = sg.d[3]; }
             } else {
               const PIX* p0 = ref + (i + ctr.ver_int - 3) * a.rstride + (j + ctr.hor_int - 3);
-#if !TK_HOST
-#pragma unroll
-#endif
+              TK_UNROLL
               for (int q = 0; q < 8; q++) { const Seg16 sg = seg_load<SP_GLOBAL, 16>(p0 + q * a.rstride); rows[q][0] = sg.d[0]; rows[q][1] = sg.d[1]; rows[q][2] = sg.d[2]; rows[q][3] = sg.d[3]; }
             }
             const int o = (int)orgs[i * a.ostride + j];
-#if !TK_HOST
-#pragma unroll
-#endif
+            TK_UNROLL
             for (int c = 0; c < 8; c++) sad8[c] += iabs(o - subk16_sample(rows, k16[c], a.bitdepth));
           }
         }
@@ -1463,9 +580,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
         if (sub_in_win) {   // the (PU + 8)^2 samples around the centre are inside the staged window
           if constexpr (sizeof(PIX) == 1) {
             const int woff = (i + ctr.ver_int - 3 - win.oy) * win.pitch + (j + ctr.hor_int - 3 - win.ox);
-#if !TK_HOST
-#pragma unroll
-#endif
+            TK_UNROLL
             for (int q = 0; q < 8; q++) { const Seg16 sg = win_seg<8>(win.w32, woff + q * win.pitch); wr[q].a = ((unsigned long long)sg.d[1] << 32) | sg.d[0]; }
           }
         } else
@@ -1474,9 +589,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
         if constexpr (sizeof(PIX) == 1) {
           unsigned long long wb[8];
           for (int q = 0; q < 8; q++) wb[q] = wr[q].a ^ 0x8080808080808080ull;   // samples - 128 as int8 lanes
-#if !TK_HOST
-#pragma unroll
-#endif
+          TK_UNROLL
           for (int c = 0; c < 8; c++) {
             const unsigned pr = (unsigned)subk8_sample(wb, k8[c]), uo = (unsigned)o;
             sad8[c] += (int)((uo > pr ? uo : pr) - (uo < pr ? uo : pr));
@@ -1498,7 +611,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
         const unsigned long long kk = ((unsigned long long)sub_cost(c, cand[c], tot) << 32) | (unsigned)c;
         k = kk < k ? kk : k;
       }
-#if defined(THOR_PROF_SUBPEL) && defined(THOR_PROF) && !TK_HOST
+#if TK_PROF_SUBPEL
       TK_PROF_ACC(w, 7, ps2_);
 #endif
     } else
@@ -1535,7 +648,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
   }
   }
   TK_PROF_ADD(w, 3);
-#if defined(THOR_PROF_ME) && defined(THOR_PROF) && !TK_HOST
+#if TK_PROF_ME
   // whole-call cycles and call counts by coding-block size (this build's code_tu does not use slots 16..25)
   if (t.rank == 0) {
     const int cls = a.cb_size <= 8 ? 0 : a.cb_size == 16 ? 1 : a.cb_size == 32 ? 2 : a.cb_size == 64 ? 3 : 4;
@@ -1557,7 +670,7 @@ TK_DEVNI unsigned motion_estimate(const Team t, MeWs* w_, const PIX* org, const 
 // predicted with the once-clipped vector, ref1 and the cost use the twice-clipped one.
 // The search has two phases: the telescope (phase bit 1), which depends only on the block, the two reference planes, mvc and mvp,
 // and the six extra candidates (phase bit 2), which read - and clobber - the candidate list as it stands after the bi-prediction
-// search of the block.  The block decision of a B frame runs the telescope early on another wavefront (tk_block.h:MD_BIJOINT) and
+// search of the block.  The block decision of a B frame runs the telescope early on another wavefront (tk_block_queue.h:md_bijoint_telescope) and
 // hands its result (min_sad_in, *mv_out) to the second phase; phase 3 = both, back to back.
 template <typename PIX, int SP>
 TK_DEVNI unsigned motion_estimate_bi(const Team t, MeWs* w_, const PIX* org_, const PIX* ref0, const PIX* ref1, const MeArgs& a,

@@ -239,9 +239,7 @@ template <int DY> TK_DEV int subk8_sample_dy(const unsigned long long* wr, const
     return sat_pix((sum + 8) >> 4, 8);
   }
   int sum = 0;
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int m = 0; m < 6; m++) {
     const unsigned long long row = wr[DY + m];
     const int h = dot4_i8((int)(unsigned)k.th8, (int)(unsigned)row, dot4_i8((int)(unsigned)(k.th8 >> 32), (int)(unsigned)(row >> 32), 128 * 64));
@@ -263,36 +261,26 @@ template <int DY> TK_DEV int subk8_strip_dy(const unsigned long long* wb, const 
   if (k.centre) {
     const unsigned long long wA = 0x0000000001010000ull << (8 * k.dx), wB = 0x0000000102020100ull << (8 * k.dx);
     int ra[12], rb[12];
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int q = 1; q < 12; q++) {
       const unsigned long long row = wb[DY + q];
       ra[q] = dot4_i8((int)(unsigned)wA, (int)(unsigned)row, dot4_i8((int)(unsigned)(wA >> 32), (int)(unsigned)(row >> 32), 0));
       rb[q] = dot4_i8((int)(unsigned)wB, (int)(unsigned)row, dot4_i8((int)(unsigned)(wB >> 32), (int)(unsigned)(row >> 32), 0));
     }
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int p = 0; p < 8; p++) sad += ad(o[p], sat_pix((128 * 16 + ra[p + 1] + rb[p + 2] + rb[p + 3] + ra[p + 4] + 8) >> 4, 8));
     return sad;
   }
   int hs[13];
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int q = 0; q < 13; q++) {
     const unsigned long long row = wb[DY + q];
     hs[q] = dot4_i8((int)(unsigned)k.th8, (int)(unsigned)row, dot4_i8((int)(unsigned)(k.th8 >> 32), (int)(unsigned)(row >> 32), 128 * 64));
   }
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int p = 0; p < 8; p++) {
     int sum = 0;
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int m = 0; m < 6; m++) sum += mul24(k.tv[m], hs[p + m]);
     sad += ad(o[p], sat_pix((sum + 2048) >> 12, 8));
   }
@@ -351,9 +339,7 @@ template <int DY, int DX> TK_DEV int subk16_sample_t(const uint32_t (*rows)[4], 
     int sum = 8;
     sum = dot2_i16(0x00010001u, row_pair16<DX>(rows[DY + 1], 1), sum);
     sum = dot2_i16(0x00010001u, row_pair16<DX>(rows[DY + 4], 1), sum);
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int m = 2; m <= 3; m++) {
       sum = dot2_i16(0x00010000u, row_pair16<DX>(rows[DY + m], 0), sum);
       sum = dot2_i16(0x00020002u, row_pair16<DX>(rows[DY + m], 1), sum);
@@ -362,9 +348,7 @@ template <int DY, int DX> TK_DEV int subk16_sample_t(const uint32_t (*rows)[4], 
     return sat_pix(sum >> 4, bitdepth);
   }
   int sum = 2048;
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int m = 0; m < 6; m++) {
     const uint32_t* d = rows[DY + m];
     const int h = dot2_i16(k.th2[0], row_pair16<DX>(d, 0), dot2_i16(k.th2[1], row_pair16<DX>(d, 1), dot2_i16(k.th2[2], row_pair16<DX>(d, 2), 0)));
@@ -393,36 +377,26 @@ TK_DEV int subk16_sample(const uint32_t (*rows)[4], const SubK16& k, int bitdept
 template <int DY, int DX> TK_DEV int subk16_strip_t(const uint32_t (*wb)[4], const SubK16& k, const int* o, int sad, int bitdepth) {
   if (k.centre) {
     int ra[12], rb[12];
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int q = 1; q < 12; q++) {
       const uint32_t* d = wb[DY + q];
       ra[q] = dot2_i16(0x00010001u, row_pair16<DX>(d, 1), 0);
       rb[q] = dot2_i16(0x00010000u, row_pair16<DX>(d, 0), dot2_i16(0x00020002u, row_pair16<DX>(d, 1), dot2_i16(0x00000001u, row_pair16<DX>(d, 2), 0)));
     }
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int p = 0; p < 8; p++) sad += iabs(o[p] - sat_pix((8 + ra[p + 1] + rb[p + 2] + rb[p + 3] + ra[p + 4]) >> 4, bitdepth));
     return sad;
   }
   int hs[13];
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int q = 0; q < 13; q++) {
     const uint32_t* d = wb[DY + q];
     hs[q] = dot2_i16(k.th2[0], row_pair16<DX>(d, 0), dot2_i16(k.th2[1], row_pair16<DX>(d, 1), dot2_i16(k.th2[2], row_pair16<DX>(d, 2), 0)));
   }
-#if !TK_HOST
-#pragma unroll
-#endif
+  TK_UNROLL
   for (int p = 0; p < 8; p++) {
     int sum = 2048;
-#if !TK_HOST
-#pragma unroll
-#endif
+    TK_UNROLL
     for (int m = 0; m < 6; m++) sum += mul24(k.tv[m], hs[p + m]);
     sad += iabs(o[p] - sat_pix(sum >> 12, bitdepth));
   }

@@ -8,7 +8,7 @@
 #include "tk_common.h"
 
 #ifndef TK_PROF_T0
-#if defined(THOR_PROF) && !TK_HOST && !defined(THOR_PROF_NOMACROS)
+#if TK_PROF_MACROS
 #ifdef THOR_PROF_WALL
 #define TK_CYC() ((long long)wall_clock64())
 #else
@@ -405,9 +405,7 @@ TK_DEV void inv_transform_recon(const Team t, XformWs* ws, const PIX* pred_, int
           const int i = k >> lg, j = (k & (ppr - 1)) << 2;
           int p[4];
           load_samples<SP, PIX, 4>(pred_ + i * pstride + j, p);
-#if !TK_HOST
-#pragma unroll
-#endif
+          TK_UNROLL
           for (int q = 0; q < 4; q++) {
             const int sum = dot_i16(mt + (j + q) * n, itmp + i * qsize, qsize, j + q);
             p[q] = sat_pix(clampi((sum + add_2) >> shift_2, -32768, 32767) + p[q], bitdepth);

@@ -123,7 +123,7 @@ int main(int argc, char** argv) {
     static const char* nm[32] = {"sb_total", "early_skip", "me_fullpel", "me_subpel", "pred_inter", "md_worker_all_waves", "code_tu", "bits", "cost", "final", "subpel_loop",
                                  "me_calls(n)", "quant", "me_telescope", "me_cands", "me_hex", "tu4", "tu8", "tu16", "tu32", "tu64+",
                                  "tu4(n)", "tu8(n)", "tu16(n)", "tu32(n)", "tu64+(n)", "wg_barrier_wait(all waves)", "bipred_lockstep(all waves, incl. barriers)", "helpers_parked(master alone)", "md_fork_to_join(master)", "tu_fwd", "tu_inv"};
-    /* THOR_PROF=md: the library was built with -DTHOR_PROF_MD (slots 16..25 = work-queue items by kind / master-alone phases, tk_block.h);
+    /* THOR_PROF=md: the library was built with -DTHOR_PROF_MD (slots 16..25 = work-queue items by kind / master-alone phases, tk_block_ws.h);
        THOR_PROF=me: -DTHOR_PROF_ME (motion-search cycles and calls by coding-block size) */
     static const char* nm_md[10] = {"items skip/merge", "items intra", "items search (MD_REF)", "items trial (incl. wait)", "trial items: wait for vectors", "queue set-up (master)",
                                     "block entry (master)", "early-skip path (master)", "final encode of decided blocks: emission (master)", "final encode of decided blocks: whole (master)"};
