@@ -236,6 +236,25 @@ int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int width, int h
  * block motion estimation per level, merge, motion-compensated average) through the engine's own device path (tk_interp_dev.h). */
 int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv);
 
+/* The motion search of one prediction unit - motion_estimate (enc/encode_block.c:517-711: telescope, candidate list incl. the 5-offset widesad of 16x16
+ * blocks, hexagon refinement, half- and quarter-pel passes, the encoder_speed 1 / 2 approximations) - on `n` items of one current / reference luma frame pair
+ * (width x height samples, no padding: the library pads the reference like a reference picture).  Each item runs the throughput build's device function in a
+ * workgroup of one wavefront with the superblock kernel's workspace (LDS search window included).  par[17*i..]: cb_x, cb_y, cb (coding block), pu_dx, pu_dy,
+ * pw, ph (prediction unit inside it), mvc.x, mvc.y, mvp.x, mvp.y (quarter-pel), sign, enable_bipred, encoder_speed, ncand, cand_off, stage (1: stage the
+ * coding block's search window around mvc first, as the HOR / VER / QUAD searches find it).  lambda[i]: the search's lambda.  cand: ncand_total full-pel list
+ * entries (x, y); item i owns [cand_off, cand_off + ncand).  out[3*i..]: mv.x, mv.y, cost.  Known answers recorded from the reference function:
+ * tests/golden/gen_kat8.py -> kat8.npz. */
+int thor_hip_kat_motion_estimate(const void* cur, const void* ref, int width, int height, int bitdepth, int n, const int* par, const double* lambda,
+                                 const int16_t* cand, int ncand_total, int* out);
+/* motion_estimate_bi (enc/encode_block.c:798-913): one vector used as +mv on ref0 and -mv on ref1.  par as above (pu = the coding block, stage ignored,
+ * cand_off = 6*i); cand: six list slots per item, the first ncand are the list on entry; list_out[12*i..]: the six slots as the call leaves them. */
+int thor_hip_kat_motion_estimate_bi(const void* cur, const void* ref0, const void* ref1, int width, int height, int bitdepth, int n, const int* par,
+                                    const double* lambda, const int16_t* cand, int* out, int16_t* list_out);
+/* The two sub-block tests of the early-skip check (enc/encode_block.c:2146-2229: check_early_skip_sub_block / _sub_blockC as the encoder executes them) on `n`
+ * items: chroma[i] 0 luma / 1 chroma, size[i] (luma 8 / 16 / 32, chroma 4 / 8 / 16), qp[i], thr[i] (early_skip_thr); org / pred: n blocks of 32x32 samples
+ * holding the size x size block in their top-left corner.  out[i]: 1 = significant.  Known answers: tests/golden/gen_kat7.py -> kat7.npz. */
+int thor_hip_kat_early_skip(const int* chroma, const void* org, const void* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out);
+
 /* Per-plane sums of squared differences between two planar 4:2:0 frames a and b (w x h; bitdepth 8: bytes, 9..12: uint16_t) through the
  * encoder's own kernel (k_frame_sse): out[0] Y, out[1] U, out[2] V, exact.  w, h: multiples of 8.  Returns 0, 1 = bad argument, 3 = no device. */
 int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth, unsigned long long out[3]);

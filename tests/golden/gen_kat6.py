@@ -2,7 +2,8 @@
 """Known answers of widesad_calc (enc/encode_block.c:430-453, file-static: reached through oracle/refshim.c) and of its SIMD kernels widesad_calc_simd_lbd /
 _hbd (enc/enc_kernels.c:84-113): the SAD at the five horizontal offsets -3 -1 0 1 3 of a candidate position, the smallest one and its offset (the LEFTMOST among
 equal ones).  The motion search evaluates the candidate list of 16x16 coding blocks with it (enc/encode_block.c:545, :570); the device restates it inside
-motion_estimate (thor_amd/csrc/tk_me.h: eval_wide), covered by the stream goldens; this file pins the ORACLE's restatement (oracle/thor_oracle.c: orc_widesad,
+motion_estimate (thor_amd/csrc/tk_me.h: eval_wide), pinned on the device by tests/test_gpu_kat.py::test_motion_estimate_matches_reference_kat (the 16x16 items of
+kat8.npz, tests/golden/gen_kat8.py); this file pins the ORACLE's restatement (oracle/thor_oracle.c: orc_widesad,
 orc_widesad16).  Build container only (`make -C oracle reflib`); writes tests/golden/kat6.npz.  Content: random, flat (every offset ties), period-2 and period-4
 columns (ties between some offsets), a ramp."""
 import ctypes as C, os, numpy as np

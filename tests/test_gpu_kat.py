@@ -263,3 +263,60 @@ def test_interpolate_frames_matches_reference_kat(bd):
     got = thor_amd.binding.kat_interpolate(K5[f'it{bd}_a'], K5[f'it{bd}_b'], W, H, bd)
     want = K5[f'it{bd}_out']
     assert (got == want).all(), int((got != want).sum())
+
+
+# ---- the motion search and the early-skip sub-block tests on the device (throughput build; the latency and the eight-wave build of the superblock kernel stay
+# covered by the stream goldens): known answers of the reference's motion_estimate / motion_estimate_bi (tests/golden/gen_kat8.py -> kat8.npz) and of its
+# check_early_skip_sub_block / _sub_blockC (gen_kat7.py -> kat7.npz) ----------------------------------------------------------------------------------------
+K8 = np.load(os.path.join(GOLD, 'kat8.npz'))
+ME_PAR = 'cb_x cb_y cb pu_dx pu_dy pw ph mvc.x mvc.y mvp.x mvp.y sign bipred speed ncand cand_off stage'.split()
+
+
+def me_failures(got, want, par, lam, lgot=None, lwant=None):
+    """The first failing items with their parameters plus got / want vector and cost."""
+    bad = np.flatnonzero((got != want).any(axis=1) | (False if lgot is None else (lgot != lwant).any(axis=(1, 2))))
+    rows = [f'{len(bad)} of {len(want)} items differ']
+    for i in bad[:6]:
+        rows.append(f'item {i}: ' + ' '.join(f'{k}={int(v)}' for k, v in zip(ME_PAR, par[i])) + f' lambda={lam[i]} got mv ({got[i][0]}, {got[i][1]}) cost {got[i][2]} want mv ({want[i][0]}, {want[i][1]}) '
+                    f'cost {want[i][2]}' + ('' if lgot is None or (lgot[i] == lwant[i]).all() else f' list got {lgot[i].tolist()} want {lwant[i].tolist()}'))
+    return len(bad), '\n'.join(rows)
+
+
+@pytest.mark.parametrize('bd', [8, 10])
+def test_motion_estimate_matches_reference_kat(bd):
+    """motion_estimate on the device (one launch, one wavefront per item, the superblock kernel's workspace and LDS search window): the LDS window per PU and
+    per CB (me_stage_cb_window), the lane-per-candidate evaluators me_cand_fullpel / me_cand8_subpel / me_cand16_subpel, the 64-lane row-segment evaluator
+    (PUs of 64 and 128 samples), eval_wide, grid and list de-duplication, the hexagon, the half- and quarter-pel passes and the encoder_speed 1 / 2
+    approximations against the reference's vector and cost, every item, bit-exact.  The speed-1 16x16 telescope items and the 16x16 list items pin eval_wide
+    against the reference's widesad_calc, ties included."""
+    import thor_amd
+    par, lam, want = K8[f'me{bd}_par'], K8[f'me{bd}_lam'], K8[f'me{bd}_out']
+    wide = (par[:, 2] == 16) & ((par[:, 14] > 0) | ((par[:, 13] == 1) & (par[:, 12] == 1)))
+    assert wide.sum() >= 100 and len(par) >= 600
+    got = thor_amd.binding.kat_motion_estimate(K8[f'f{bd}_cur'], K8[f'f{bd}_ref'], par, lam, K8[f'me{bd}_cand'], bd)
+    nbad, rep = me_failures(got, want, par, lam)
+    assert nbad == 0, rep
+
+
+@pytest.mark.parametrize('bd', [8, 10])
+def test_motion_estimate_bi_matches_reference_kat(bd):
+    """motion_estimate_bi on the device: vector, cost and the candidate list as the call leaves it (slots num..3 zero-filled, 4 and 5 overwritten), CBs 8 .. 64,
+    both signs, blocks whose vector the second clip changes."""
+    import thor_amd
+    par, lam, want, lwant = K8[f'bi{bd}_par'], K8[f'bi{bd}_lam'], K8[f'bi{bd}_out'], K8[f'bi{bd}_list']
+    assert len(par) >= 100
+    got, lgot = thor_amd.binding.kat_motion_estimate_bi(K8[f'f{bd}_cur'], K8[f'f{bd}_ref'], K8[f'f{bd}_ref1'], par, lam, K8[f'bi{bd}_cand'], bd)
+    nbad, rep = me_failures(got, want, par, lam, lgot, lwant)
+    assert nbad == 0, rep
+
+
+def test_early_skip_sub_block_tests_match_reference_kat():
+    """early_skip_sub / early_skip_subC (tk_block.h) on the device against the 288 answers of kat7.npz (luma 8 / 16 / 32, chroma 4 / 8 / 16, three qp, two
+    thresholds, residuals around the decision boundary)."""
+    import thor_amd
+    K7 = np.load(os.path.join(GOLD, 'kat7.npz'))
+    arg, want = K7['es_arg'], K7['es_out']
+    assert len(want) == 288
+    got = thor_amd.binding.kat_early_skip(arg[:, 0], K7['es_org'], K7['es_pred'], arg[:, 1], arg[:, 2], arg[:, 3] / 10.0, 8)
+    bad = np.flatnonzero(got != want)
+    assert not len(bad), (len(bad), [(int(i), arg[i].tolist(), int(got[i]), int(want[i])) for i in bad[:6]])

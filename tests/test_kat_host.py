@@ -1,6 +1,7 @@
 """Round 6: the known answers of tests/golden/kat5.npz (recorded from the reference functions, tests/golden/gen_kat5.py) against the 1-lane HOST build of the
 device functions (tests/hostsim/kat_host.cpp: make_edges + pred_intra, the two CLPF passes, cdef_find_dir, cdef_filter_px) - the CPU twin of the
-device known-answer tests (tests/test_gpu_kat.py), bitdepth 8 / 10 / 12."""
+device known-answer tests (tests/test_gpu_kat.py), bitdepth 8 / 10 / 12.  The motion search: the known answers of tests/golden/kat8.npz (the reference's
+motion_estimate / motion_estimate_bi, tests/golden/gen_kat8.py) against the host build of tk_me.h (tests/hostsim/kat_host_me.cpp), 1-lane and 64-lane teams."""
 import ctypes as C
 import os
 import subprocess
@@ -77,3 +78,88 @@ def test_early_skip_sub_block_tests_host_build_match_reference_kat(tmp_path):
         chroma, size, qp, thr10 = (int(v) for v in arg[k])
         got = H.h_early_skip_sub(chroma, P(org[k]), 32, P(pred[k]), 32, size, qp, thr10 / 10.0, 8)
         assert got == int(want[k]), (k, chroma, size, qp, thr10, got, int(want[k]))
+
+
+# ---- the motion search: motion_estimate / motion_estimate_bi / me_stage_cb_window (thor_amd/csrc/tk_me.h) against the reference's own answers ---------------------
+K8 = np.load(os.path.join(ROOT, 'tests', 'golden', 'kat8.npz'))
+ME_PAD = 160   # kPadY: the replicate padding of a reference picture (k_make_ref)
+ME_PAR = 'cb_x cb_y cb pu_dx pu_dy pw ph mvc.x mvc.y mvp.x mvp.y sign bipred speed ncand cand_off stage'.split()
+
+
+def me_planes(bd):
+    """cur, ref0, ref1 with the replicate padding, and the offset (in samples) of sample (0, 0)."""
+    pl = [np.ascontiguousarray(np.pad(K8[f'f{bd}_{k}'], ME_PAD, mode='edge')) for k in ('cur', 'ref', 'ref1')]
+    return pl, ME_PAD * pl[0].shape[1] + ME_PAD
+
+
+def me_host_batch(lib, bd, lanes, bi, sel=None):
+    """Vector, cost (and list afterwards) of the items `sel` (default: all) of kat8.npz from the host build; returns (got, want, list_got, list_want, par)."""
+    pre = ('bi' if bi else 'me') + str(bd)
+    par, lam, cand, want = (np.ascontiguousarray(K8[f'{pre}_{k}']) for k in ('par', 'lam', 'cand', 'out'))
+    lwant = K8[f'{pre}_list'] if bi else None
+    if sel is not None:
+        par, lam, want = np.ascontiguousarray(par[sel]), np.ascontiguousarray(lam[sel]), want[sel]
+        lwant = lwant[sel] if bi else None
+    (cur, r0, r1), o = me_planes(bd)
+    S = cur.itemsize
+    H, W = K8[f'f{bd}_cur'].shape
+    got = np.full((len(par), 3), -1, dtype=np.int32)
+    lgot = np.zeros((len(par), 6, 2), dtype=np.int16)
+    at = lambda a: C.c_void_p(a.ctypes.data + o * S)
+    rc = lib.h_me_batch(bi, bd, lanes, at(cur), at(r0), at(r1), cur.shape[1], W, H, len(par), P(par), P(lam), P(cand), P(got), P(lgot))
+    assert rc == 0
+    return got, want, lgot, lwant, par
+
+
+def me_report(got, want, par, lam=None, lgot=None, lwant=None):
+    """The first failing items with their parameters plus got / want vector and cost (None when everything matches)."""
+    bad = np.flatnonzero((got != want).any(axis=1) | (False if lgot is None else (lgot != lwant).any(axis=(1, 2))))
+    if not len(bad):
+        return None
+    rows = [f'{len(bad)} of {len(want)} items differ']
+    for i in bad[:6]:
+        rows.append(f'item {i}: ' + ' '.join(f'{k}={int(v)}' for k, v in zip(ME_PAR, par[i])) + f' got mv ({got[i][0]}, {got[i][1]}) cost {got[i][2]} want mv ({want[i][0]}, {want[i][1]}) cost {want[i][2]}'
+                    + ('' if lgot is None or (lgot[i] == lwant[i]).all() else f' list got {lgot[i].tolist()} want {lwant[i].tolist()}'))
+    return '\n'.join(rows)
+
+
+def build_me_host(d, lanes64):
+    so = str(d / ('kat_host_me64.so' if lanes64 else 'kat_host_me.so'))
+    extra = ['-O2', '-DTHOR_HOSTSIM_LANES=64', '-pthread'] if lanes64 else ['-O1']
+    subprocess.check_call(['g++', '-std=c++17', '-fno-strict-aliasing', '-DTHOR_HOSTSIM', '-ffp-contract=off', '-shared', '-fPIC'] + extra + ['-o', so,
+                           os.path.join(ROOT, 'tests', 'hostsim', 'kat_host_me.cpp')])
+    return C.CDLL(so)
+
+
+def me_lanes64_slice(bd):
+    """The fixed slice the 64-lane host team runs (64 OS threads per team: slow): every 7th (8 bit) / 10th (10 bit) search of up to 32x32 samples at
+    encoder_speed 0 - what takes the lane-per-candidate evaluators - in fixture order, at most 140 + 60 items."""
+    par = K8[f'me{bd}_par']
+    small = np.flatnonzero((par[:, 5] <= 32) & (par[:, 6] <= 32) & (par[:, 13] == 0))
+    return small[::7][:140] if bd == 8 else small[::10][:60]
+
+
+def test_motion_search_host_build_matches_reference_kat(tmp_path):
+    """Every item of kat8.npz - motion_estimate (all PU shapes 4x4 .. 128x128, frame corners / edges / interior / tie bands, predictors on, near, far off and
+    beyond the frame, both signs and filter sets, encoder_speed 0 / 1 / 2, three lambdas, candidate lists of 0 .. 48 entries incl. the 5-offset widesad of 16x16
+    CBs, HOR / VER / QUAD sets on a staged CB window) and motion_estimate_bi (CBs 8 .. 64, 0 .. 6 list entries, the second clip, the list side effect) at
+    bitdepth 8 and 10 - bit-exact in vector, cost and list against the reference's answers, with the 1-lane host build; and a fixed slice of 200 searches with a
+    64-lane host team, i.e. the lane-per-candidate code of tk_me_lanes.h against the reference itself.
+    (Sensitivity checked once by hand: a reversed tie-break in me_cand_fullpel's range_min fails 18 of the 194 searches of the 64-lane slice; a rate term off by one
+    quarter-pel fails 79 of them when put into me_cand_fullpel and 897 of the 2496 motion_estimate items of the 1-lane build when put into rate_of.)"""
+    L1 = build_me_host(tmp_path, False)
+    for bd in (8, 10):
+        for bi in (0, 1):
+            got, want, lgot, lwant, par = me_host_batch(L1, bd, 1, bi)
+            assert len(want) >= (100 if bi else 600)
+            rep = me_report(got, want, par, None, lgot if bi else None, lwant)
+            assert rep is None, f'1-lane host build, bitdepth {bd}, {"motion_estimate_bi" if bi else "motion_estimate"}: {rep}'
+    L64 = build_me_host(tmp_path, True)
+    total = 0
+    for bd in (8, 10):
+        sel = me_lanes64_slice(bd)
+        total += len(sel)
+        got, want, _, _, par = me_host_batch(L64, bd, 64, 0, sel)
+        rep = me_report(got, want, par)
+        assert rep is None, f'64-lane host team, bitdepth {bd}: {rep}'
+    assert 150 <= total <= 200

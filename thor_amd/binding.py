@@ -433,6 +433,42 @@ def kat_interpolate(yuv0, yuv1, width, height, bitdepth=8):
     return out
 
 
+def kat_motion_estimate(cur, ref, par, lam, cand, bitdepth=8):
+    """thor_hip_kat_motion_estimate: the device motion search on len(par) items of one current / reference luma pair; returns (n, 3) mv.x, mv.y, cost."""
+    T = _pix(bitdepth)
+    cur = np.ascontiguousarray(cur, dtype=T); ref = np.ascontiguousarray(ref, dtype=T)
+    par = np.ascontiguousarray(par, dtype=np.int32); lam = np.ascontiguousarray(lam, dtype=np.float64); cand = np.ascontiguousarray(cand, dtype=np.int16).reshape(-1, 2)
+    assert cur.shape == ref.shape and par.shape[1] == 17 and len(lam) == len(par)
+    out = np.full((len(par), 3), -1, dtype=np.int32)
+    _kat('thor_hip_kat_motion_estimate', _vp(cur), _vp(ref), cur.shape[1], cur.shape[0], bitdepth, len(par), _vp(par), _vp(lam), _vp(cand), len(cand), _vp(out))
+    return out
+
+
+def kat_motion_estimate_bi(cur, ref0, ref1, par, lam, cand, bitdepth=8):
+    """thor_hip_kat_motion_estimate_bi; cand: (n, 6, 2) list slots.  Returns ((n, 3) mv.x, mv.y, cost, (n, 6, 2) the list afterwards)."""
+    T = _pix(bitdepth)
+    cur, ref0, ref1 = (np.ascontiguousarray(a, dtype=T) for a in (cur, ref0, ref1))
+    par = np.ascontiguousarray(par, dtype=np.int32); lam = np.ascontiguousarray(lam, dtype=np.float64); cand = np.ascontiguousarray(cand, dtype=np.int16)
+    assert cur.shape == ref0.shape == ref1.shape and par.shape[1] == 17 and len(lam) == len(par) and cand.size == 12 * len(par)
+    out = np.full((len(par), 3), -1, dtype=np.int32)
+    lists = np.zeros((len(par), 6, 2), dtype=np.int16)
+    _kat('thor_hip_kat_motion_estimate_bi', _vp(cur), _vp(ref0), _vp(ref1), cur.shape[1], cur.shape[0], bitdepth, len(par), _vp(par), _vp(lam), _vp(cand), _vp(out), _vp(lists))
+    return out, lists
+
+
+def kat_early_skip(chroma, org, pred, size, qp, thr, bitdepth=8):
+    """thor_hip_kat_early_skip: org / pred (n, 32, 32) blocks; chroma / size / qp / thr per item.  Returns the n decisions (1 = significant)."""
+    T = _pix(bitdepth)
+    org = np.ascontiguousarray(org, dtype=T); pred = np.ascontiguousarray(pred, dtype=T)
+    chroma, size, qp = (np.ascontiguousarray(a, dtype=np.int32) for a in (chroma, size, qp))
+    thr = np.ascontiguousarray(thr, dtype=np.float32)
+    n = len(org)
+    assert org.shape == pred.shape == (n, 32, 32) and len(chroma) == len(size) == len(qp) == len(thr) == n
+    out = np.full(n, -1, dtype=np.int32)
+    _kat('thor_hip_kat_early_skip', _vp(chroma), _vp(org), _vp(pred), _vp(size), _vp(qp), _vp(thr), bitdepth, n, _vp(out))
+    return out
+
+
 def frame_sse(a, b, width, height, bitdepth=8):
     """Per-plane (Y, U, V) sums of squared differences of two planar 4:2:0 frames on the GPU (thor_hip_frame_sse, kernel k_frame_sse)."""
     T = _pix(bitdepth)

@@ -100,6 +100,84 @@ __global__ __launch_bounds__(64) void k_kat_cdef_filter(const PIX* plane, int w,
   const int x = q[0] + k % bsize, y = q[1] + k / bsize;
   out[(size_t)it * bsize * bsize + k] = (PIX)cdef_filter_px(plane, stride, x, y, w, h, q[2], q[3], q[4], q[5], q[6], cs);
 }
+// ---- the motion search and the early-skip sub-block tests: one workgroup of one wavefront per item, the workspace built as the superblock kernel builds it
+// (make_ws: WgShared + SmallWs in LDS, the search window in the transform workspace + win_extra with the product's win_cap).  motion_estimate /
+// motion_estimate_bi are __noinline__ functions the superblock kernel calls too, so these kernels carry its launch bounds (see k_kat_inter_yuv above).
+// par[kKatMePar * i ..]: cb_x, cb_y, cb, pu_dx, pu_dy, pw, ph, mvc.x, mvc.y, mvp.x, mvp.y, sign, enable_bipred, encoder_speed, ncand, cand_off, stage
+enum { kKatMePar = 17 };
+template <typename PIX>
+__global__ __launch_bounds__(kWgThreads, (sizeof(PIX) == 1 ? (int)kOcc : 2)) void k_kat_me(int bi, Plane3<PIX> cur, Plane3<PIX> ref0, Plane3<PIX> ref1, int fw, int fh, int bitdepth,
+                                                                                           const int* par, const double* lam, const int16_t* cand, unsigned char* big, int* out,
+                                                                                           int16_t* list_out) {
+  __shared__ WgShared sh;
+  __shared__ SmallWs<PIX> sws;
+  const int lane = (int)threadIdx.x, it = (int)blockIdx.x;
+  TeamWs<PIX> ws = make_ws(&sws, &sh, (BigWs<PIX>*)big);
+  const Team t = mk_team(lane, 64, sh.tabs.izz);
+  xform_tables_fill(&sh.tabs, lane, 64);
+  const int* q = par + kKatMePar * it;
+  const int cbx = q[0], cby = q[1], cb = q[2], pux = cbx + q[3], puy = cby + q[4];
+  MeLists* lists = &sh.lists;
+  const int nl = bi ? 6 : q[14];
+  for (int c = lane; c < nl; c += 64) { lists->mvcand[0][c].x = cand[2 * (q[15] + c)]; lists->mvcand[0][c].y = cand[2 * (q[15] + c) + 1]; }
+  if (lane == 0) { lists->mvcand_num[0] = q[14]; lists->mvcand_mask[0] = 0; lists->best_ref = 0; }
+  // the original block: the workgroup's LDS copy (stride = CB size) for CBs up to kLdsBlk, the frame plane above (org_select)
+  const int lds_blk = __builtin_amdgcn_readfirstlane(cb <= kLdsBlk);
+  PIX* orgc = (PIX*)sh.org_raw;
+  if (lds_blk)
+    for (int k = lane; k < cb * cb; k += 64) orgc[k] = cur.y[(size_t)(cby + k / cb) * cur.sy + cbx + k % cb];
+  __syncthreads();
+  MeArgs a;
+  a.cb_size = cb; a.ostride = lds_blk ? cb : cur.sy; a.width = q[5]; a.height = q[6]; a.rstride = ref0.sy; a.sign = q[11]; a.fwidth = fw; a.fheight = fh;
+  a.xpos = cbx; a.ypos = cby; a.pu_x = pux; a.pu_y = puy; a.enable_bipred = q[12]; a.bitdepth = bitdepth; a.speed = q[13]; a.lam = lam[it];
+  const mv_t mvc = mk_mv(q[7], q[8]), mvp = mk_mv(q[9], q[10]);
+  const PIX* org = lds_blk ? orgc + q[4] * cb + q[3] : cur.y + (size_t)puy * cur.sy + pux;
+  mv_t mv = mk_mv(0, 0);
+  unsigned cost;
+  if (bi) {
+    const PIX* r0 = ref0.y + (size_t)cby * ref0.sy + cbx;
+    const PIX* r1 = ref1.y + (size_t)cby * ref1.sy + cbx;
+    cost = lds_blk ? motion_estimate_bi<PIX, SP_LDS>(t, ws.mep, org, r0, r1, a, mvc, mvp, 0, &mv) : motion_estimate_bi<PIX, SP_GLOBAL>(t, ws.mep, org, r0, r1, a, mvc, mvp, 0, &mv);
+  } else {
+    if (q[16]) me_stage_cb_window<PIX>(t, ws.mep, ref0.y + (size_t)cby * ref0.sy + cbx, ref0.sy, cbx, cby, cb, mvc, a.sign, fw, fh, 0);
+    const PIX* rp = ref0.y + (size_t)puy * ref0.sy + pux;
+    cost = lds_blk ? motion_estimate<PIX, SP_LDS>(t, ws.mep, org, rp, a, mvc, mvp, 0, &mv) : motion_estimate<PIX, SP_GLOBAL>(t, ws.mep, org, rp, a, mvc, mvp, 0, &mv);
+  }
+  __syncthreads();
+  if (lane == 0) { out[3 * it] = mv.x; out[3 * it + 1] = mv.y; out[3 * it + 2] = (int)cost; }
+  if (bi && lane < 6) { list_out[12 * it + 2 * lane] = lists->mvcand[0][lane].x; list_out[12 * it + 2 * lane + 1] = lists->mvcand[0][lane].y; }
+}
+// early_skip_sub / early_skip_subC (tk_block.h) on item blockIdx.x: org / pred are blocks of 32x32 samples with the size x size block in their top-left corner;
+// blocks the product keeps in LDS (luma up to kLdsBlk, chroma up to kLdsBlk / 2) are copied there and take the SP_LDS instance, as in check_early_skip
+template <typename PIX>
+__global__ __launch_bounds__(kWgThreads, (sizeof(PIX) == 1 ? (int)kOcc : 2)) void k_kat_early_skip(const int* chroma, const PIX* org, const PIX* pred, const int* size, const int* qp,
+                                                                                                   const float* thr, int bitdepth, unsigned char* big, int* out) {
+  __shared__ FrameJob<PIX> sJ;
+  __shared__ WgShared sh;
+  __shared__ SmallWs<PIX> sws;
+  __shared__ TeamWs<PIX> s_view;
+  const int lane = (int)threadIdx.x, it = (int)blockIdx.x;
+  lds_st(&s_view, make_ws(&sws, &sh, (BigWs<PIX>*)big));
+  WsP<PIX> ws = ldsc(&s_view);
+  JobR<PIX> J = *ldsc(&sJ);
+  const Team t = mk_team(lane, 64, sh.tabs.izz);
+  xform_tables_fill(&sh.tabs, lane, 64);
+  if (lane == 0) sJ.cfg.bitdepth = bitdepth;
+  const int ch = __builtin_amdgcn_readfirstlane(chroma[it]), n = __builtin_amdgcn_readfirstlane(size[it]), qpi = __builtin_amdgcn_readfirstlane(qp[it]);
+  const float th = thr[it];
+  const PIX* o = org + (size_t)it * 1024;
+  const PIX* p = pred + (size_t)it * 1024;
+  const int lds_blk = n <= (ch ? kLdsBlk / 2 : kLdsBlk);
+  PIX* lo = sws.lbuf;
+  PIX* lp = sws.lbuf + kLdsBlk * kLdsBlk;
+  if (lds_blk)
+    for (int k = lane; k < n * n; k += 64) { lo[k] = o[(k / n) * 32 + k % n]; lp[k] = p[(k / n) * 32 + k % n]; }
+  __syncthreads();
+  int r;
+  if (ch) r = lds_blk ? early_skip_subC<PIX, SP_LDS>(t, J, ws, lo, n, lp, n, n, qpi, th) : early_skip_subC<PIX, SP_GLOBAL>(t, J, ws, o, 32, p, 32, n, qpi, th);
+  else r = lds_blk ? early_skip_sub<PIX, SP_LDS>(t, J, ws, lo, n, lp, n, n, qpi, th) : early_skip_sub<PIX, SP_GLOBAL>(t, J, ws, o, 32, p, 32, n, qpi, th);
+  if (lane == 0) out[it] = r;
+}
 }  // namespace tk
 
 template <typename PIX>
@@ -368,6 +446,70 @@ template <typename PIX> int kat_interpolate(const PIX* yuv0, const PIX* yuv1, in
   delete eng;
   return 0;
 }
+// motion_estimate / motion_estimate_bi / me_stage_cb_window (tk_me.h) on `n` items of one current / reference luma frame pair (bi: two references)
+template <typename PIX> DevFrame<PIX> kat_luma_frame(const PIX* luma, int width, int height, int pad_ref) {
+  std::vector<PIX> yuv((size_t)width * height * 3 / 2, (PIX)0);
+  memcpy(yuv.data(), luma, (size_t)width * height * sizeof(PIX));
+  if (pad_ref) return kat_padded_ref(yuv.data(), width, height);
+  DevFrame<PIX> f;
+  f.alloc(width, height, 0);
+  upload_yuv(f, yuv.data(), width, height);
+  return f;
+}
+template <typename PIX>
+int kat_me(int bi, const PIX* cur, const PIX* ref0, const PIX* ref1, int width, int height, int bitdepth, int n, const int* par, const double* lam, const int16_t* cand,
+           int ncand_total, int* out, int16_t* list_out) {
+  if (!cur || !ref0 || (bi && (!ref1 || !list_out)) || !par || !lam || !out || n <= 0 || ncand_total < 0 || (ncand_total && !cand) || width % 8 || height % 8 || width < 16 ||
+      height < 16 || width > 8192 || height > 8192)
+    return 1;
+  auto pow2 = [](int v, int lo, int hi) { return v >= lo && v <= hi && !(v & (v - 1)); };
+  for (int i = 0; i < n; i++) {
+    const int* q = par + kKatMePar * i;
+    if (!pow2(q[2], 8, kMaxSb) || !pow2(q[5], 4, q[2]) || !pow2(q[6], 4, q[2]) || (q[11] & ~1) || (q[12] & ~1) || q[13] < 0 || q[13] > 2 || !(lam[i] >= 0.0 && lam[i] <= 1e6)) return 1;
+    if (q[0] < 0 || q[1] < 0 || q[0] + q[2] > width || q[1] + q[2] > height || q[3] < 0 || q[4] < 0 || q[3] + q[5] > q[2] || q[4] + q[6] > q[2] || q[3] % 4 || q[4] % 4) return 2;
+    for (int k = 7; k <= 10; k++) if (q[k] < -8192 || q[k] > 8192) return 1;   // vectors are int16 quarter-pels; the search adds up to +-128 to them
+    const int slots = bi ? 6 : q[14];
+    if (q[14] < 0 || q[14] > (bi ? 6 : 64) || q[15] < 0 || q[15] + slots > ncand_total) return 2;
+    if (bi && (q[3] || q[4] || q[5] != q[2] || q[6] != q[2])) return 1;
+    for (int c = 0; c < slots; c++) if (cand[2 * (q[15] + c)] < -2047 || cand[2 * (q[15] + c)] > 2047 || cand[2 * (q[15] + c) + 1] < -2047 || cand[2 * (q[15] + c) + 1] > 2047) return 1;
+  }
+  if (!ensure_init_any()) return 3;
+  DevFrame<PIX> fc = kat_luma_frame(cur, width, height, 0), f0 = kat_luma_frame(ref0, width, height, 1), f1 = bi ? kat_luma_frame(ref1, width, height, 1) : DevFrame<PIX>();
+  {
+    DevBuf<int> d_par((size_t)kKatMePar * n, par);
+    DevBuf<double> d_lam(n, lam);
+    DevBuf<int16_t> d_cand((size_t)2 * (ncand_total ? ncand_total : 1));
+    if (ncand_total) backend::h2d(d_cand, cand, (size_t)4 * ncand_total);
+    DevBuf<unsigned char> d_big(sizeof(BigWs<PIX>));   // the per-wave global scratch make_ws points at; the searches do not touch it
+    DevBuf<int> d_o((size_t)3 * n);
+    DevBuf<int16_t> d_l((size_t)12 * n);
+    hipLaunchKernelGGL(k_kat_me<PIX>, dim3(n), dim3(64), 0, g_stream, bi, fc.p, f0.p, bi ? f1.p : f0.p, width, height, bitdepth, d_par, d_lam, d_cand, d_big, d_o, d_l);
+    HIPCHECK(hipGetLastError());
+    backend::d2h(out, d_o, (size_t)3 * n * 4);
+    if (bi) backend::d2h(list_out, d_l, (size_t)12 * n * 2);
+  }
+  fc.release(); f0.release();
+  if (bi) f1.release();
+  return 0;
+}
+template <typename PIX>
+int kat_early_skip(const int* chroma, const PIX* org, const PIX* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out) {
+  if (!chroma || !org || !pred || !size || !qp || !thr || !out || n <= 0) return 1;
+  for (int i = 0; i < n; i++) {
+    const int s = size[i];
+    if ((chroma[i] & ~1) || qp[i] < 0 || qp[i] > 51 || !(thr[i] >= 0.0f && thr[i] <= 1e3f)) return 1;
+    if (chroma[i] ? (s != 4 && s != 8 && s != 16) : (s != 8 && s != 16 && s != 32)) return 2;
+  }
+  if (!ensure_init_any()) return 3;
+  DevBuf<PIX> d_org((size_t)n * 1024, org), d_pred((size_t)n * 1024, pred);
+  DevBuf<int> d_ch(n, chroma), d_size(n, size), d_qp(n, qp), d_o(n);
+  DevBuf<float> d_thr(n, thr);
+  DevBuf<unsigned char> d_big(sizeof(BigWs<PIX>));
+  hipLaunchKernelGGL(k_kat_early_skip<PIX>, dim3(n), dim3(64), 0, g_stream, d_ch, d_org, d_pred, d_size, d_qp, d_thr, bitdepth, d_big, d_o);
+  HIPCHECK(hipGetLastError());
+  backend::d2h(out, d_o, (size_t)n * 4);
+  return 0;
+}
 }  // namespace
 #define KAT_BD(call8, call16) do { if (bitdepth == 8) return call8; if (bitdepth >= 9 && bitdepth <= 12) return call16; return 1; } while (0)
 extern "C" int thor_hip_kat_intra(const void* plane, int width, int height, int stride, int bitdepth, int size, int tb_split, int n, const int* par,
@@ -398,6 +540,20 @@ extern "C" int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int w
                                  const int* strength, int fb_log2, const uint8_t* fb_on, uint32_t* stats, void* out_yuv) {
   KAT_BD(kat_clpf<uint8_t>((const uint8_t*)rec_yuv, (const uint8_t*)org_yuv, width, height, 8, qp, cells, strength, fb_log2, fb_on, stats, (uint8_t*)out_yuv),
          kat_clpf<uint16_t>((const uint16_t*)rec_yuv, (const uint16_t*)org_yuv, width, height, bitdepth, qp, cells, strength, fb_log2, fb_on, stats, (uint16_t*)out_yuv));
+}
+extern "C" int thor_hip_kat_motion_estimate(const void* cur, const void* ref, int width, int height, int bitdepth, int n, const int* par, const double* lambda,
+                                            const int16_t* cand, int ncand_total, int* out) {
+  KAT_BD(kat_me<uint8_t>(0, (const uint8_t*)cur, (const uint8_t*)ref, nullptr, width, height, 8, n, par, lambda, cand, ncand_total, out, nullptr),
+         kat_me<uint16_t>(0, (const uint16_t*)cur, (const uint16_t*)ref, nullptr, width, height, bitdepth, n, par, lambda, cand, ncand_total, out, nullptr));
+}
+extern "C" int thor_hip_kat_motion_estimate_bi(const void* cur, const void* ref0, const void* ref1, int width, int height, int bitdepth, int n, const int* par,
+                                               const double* lambda, const int16_t* cand, int* out, int16_t* list_out) {
+  KAT_BD(kat_me<uint8_t>(1, (const uint8_t*)cur, (const uint8_t*)ref0, (const uint8_t*)ref1, width, height, 8, n, par, lambda, cand, 6 * n, out, list_out),
+         kat_me<uint16_t>(1, (const uint16_t*)cur, (const uint16_t*)ref0, (const uint16_t*)ref1, width, height, bitdepth, n, par, lambda, cand, 6 * n, out, list_out));
+}
+extern "C" int thor_hip_kat_early_skip(const int* chroma, const void* org, const void* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out) {
+  KAT_BD(kat_early_skip<uint8_t>(chroma, (const uint8_t*)org, (const uint8_t*)pred, size, qp, thr, 8, n, out),
+         kat_early_skip<uint16_t>(chroma, (const uint16_t*)org, (const uint16_t*)pred, size, qp, thr, bitdepth, n, out));
 }
 // Per-plane SSE of two host frames through k_frame_sse (the kernel the engine launches with frame distortion on).
 template <typename PIX> int frame_sse_host(const PIX* a, const PIX* b, int width, int height, unsigned long long out[3]) {
