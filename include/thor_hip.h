@@ -254,6 +254,26 @@ int thor_hip_kat_motion_estimate_bi(const void* cur, const void* ref0, const voi
  * items: chroma[i] 0 luma / 1 chroma, size[i] (luma 8 / 16 / 32, chroma 4 / 8 / 16), qp[i], thr[i] (early_skip_thr); org / pred: n blocks of 32x32 samples
  * holding the size x size block in their top-left corner.  out[i]: 1 = significant.  Known answers: tests/golden/gen_kat7.py -> kat7.npz. */
 int thor_hip_kat_early_skip(const int* chroma, const void* org, const void* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out);
+/* The block syntax writer and its bit counter (thor_amd/csrc/tk_bits.h) on `n` items, one wavefront per item, against bit strings recorded from the reference's
+ * put_vlc (enc/putvlc.c:73-160), write_mv (enc/write_bits.c:123-143), write_coeff (:145-241), write_super_mode (:257-358) and write_block (:360-600):
+ * tests/golden/gen_kat9.py -> kat9.npz.  Bit strings are arrays of 32-bit words, word w = bits [32w, 32w + 32), first bit in the MSB; every item owns `words`
+ * words of each buffer.  Return 0, 1 = bad argument, 2 = an item reaches outside a given buffer, 3 = no usable device.
+ * The two syntax entry points run a compilation of tk_bits.h of their own (thor_amd/csrc/thor_hip_katbits.cpp: same source, flags and parameters as the throughput
+ * build, kept apart so that the superblock kernels' code stays what it was); the throughput build's own binary of these functions is covered by the stream goldens.
+ * write_coeff: par[4*i..]: size (4 .. 128, the transform unit's; min(size, 16)^2 coefficients are coded), type (bit 0 chroma, bit 1 intra block), the bit
+ * position the string starts at (0 .. 63), the capacity in bits (<= 32 * words).  coef: 256 coefficients per item, row-major in the first min(size, 16)^2.
+ * buf_single / buf_team (in / out, pre-filled by the caller): written by bs_coeff on one lane / by bs_coeff_team on 64 lanes between bs_open and bs_close.
+ * out[6*i..]: coeff_bits_team<SP_LDS>, coeff_bits_team<SP_GLOBAL>, final position and overflow flag of bs_coeff, the same of bs_coeff_team. */
+int thor_hip_kat_coeff_syntax(int n, const int* par, const int16_t* coef, int words, uint32_t* buf_single, uint32_t* buf_team, int* out);
+/* write_block / write_super_mode / one put_vlc codeword / one write_mv.  par[57*i..] and out[10*i..]: the rows thor_amd/csrc/tk_kat_bits.h describes (SynCtx and
+ * BlkParam flat, then the index into `pool` of each transform unit's coefficients; counts of bs_block_head_t<false>, of bs_block_t<false, SP_LDS / SP_GLOBAL>
+ * without and with ybits, length and overflow flag of the cooperative and of the single-lane emission).  pool: npool blocks of 256 coefficients.  buf_coop /
+ * buf_single (in / out): written from bit 0 by bs_block_t<true> with a team / by one lane, capacity 32 * words bits. */
+int thor_hip_kat_block_syntax(int n, const int* par, const int16_t* pool, int npool, int words, uint32_t* buf_coop, uint32_t* buf_single, int* out);
+/* k_gather_bits, the kernel that concatenates the superblocks' strings into a frame payload: string i = nbits[i] bits starting at word src_off[i] of `src`
+ * (src_words words; bits of its last word beyond nbits are arbitrary), placed at bit dst_bit[i] of a zeroed destination of dst_words words.  Return 0, 1 = bad argument, 2 = a string reaches outside
+ * `src` or the destination, 3 = no usable device. */
+int thor_hip_kat_gather_bits(int n, const uint32_t* src, int src_words, const int* src_off, const int* nbits, const long long* dst_bit, uint32_t* dst, int dst_words);
 
 /* Per-plane sums of squared differences between two planar 4:2:0 frames a and b (w x h; bitdepth 8: bytes, 9..12: uint16_t) through the
  * encoder's own kernel (k_frame_sse): out[0] Y, out[1] U, out[2] V, exact.  w, h: multiples of 8.  Returns 0, 1 = bad argument, 3 = no device. */

@@ -103,4 +103,94 @@ void ref_detect_multi_clpf(const uint8_t* rec, const uint8_t* org, int x0, int y
   if (simd) detect_multi_clpf_simd_lbd(rec, org, x0, y0, width, height, ostride, rstride, sum, shift, size, dmp);
   else detect_multi_clpf_lbd(rec, org, x0, y0, width, height, ostride, rstride, sum, shift, size, dmp);
 }
+/* ---- the block syntax as bit STRINGS (tests/golden/gen_kat9.py): every wrapper writes into a fresh stream_t, returns the bit length and copies the string
+ * - bitstream[0..bytepos) followed by the top 32 - bitrest bits of bitbuf - to out (at most out_bytes bytes). */
+static uint8_t syn_buf[1 << 17];
+static void syn_open(stream_t* s) {
+  memset(syn_buf, 0, sizeof syn_buf);
+  s->bytesize = sizeof syn_buf; s->bytepos = 0; s->bitstream = syn_buf; s->bitbuf = 0; s->bitrest = 32;
+}
+static int syn_close(stream_t* s, uint8_t* out, int out_bytes) {
+  int nbits = get_bit_pos(s), n = 0;
+  for (uint32_t i = 0; i < s->bytepos && n < out_bytes; i++) out[n++] = s->bitstream[i];
+  for (int k = 0; k < (int)(32 - s->bitrest + 7) / 8 && n < out_bytes; k++) out[n++] = (uint8_t)(s->bitbuf >> (24 - 8 * k));
+  return nbits;
+}
+/* put_vlc (enc/putvlc.c:73-160): one codeword of table n */
+int ref_put_vlc(int n, unsigned cn, uint8_t* out, int out_bytes) {
+  stream_t s;
+  syn_open(&s);
+  put_vlc(n, cn, &s);
+  return syn_close(&s, out, out_bytes);
+}
+/* write_mv (enc/write_bits.c:123-143) */
+int ref_write_mv(int mvx, int mvy, int mvpx, int mvpy, uint8_t* out, int out_bytes) {
+  stream_t s;
+  mv_t mv, mvp;
+  mv.x = (int16_t)mvx; mv.y = (int16_t)mvy; mvp.x = (int16_t)mvpx; mvp.y = (int16_t)mvpy;
+  syn_open(&s);
+  write_mv(&s, &mv, &mvp);
+  return syn_close(&s, out, out_bytes);
+}
+/* write_coeff (enc/write_bits.c:145-241) */
+int ref_write_coeff(int16_t* coeff, int size, int type, uint8_t* out, int out_bytes) {
+  stream_t s;
+  syn_open(&s);
+  write_coeff(&s, coeff, size, type);
+  return syn_close(&s, out, out_bytes);
+}
+/* The flat parameter row of a kat9.npz block item (tests/golden/gen_kat9.py: BL_PAR): 0 kind, 1 split_flag, 2 frame_type, 3 num_ref, 4 enable_bipred,
+ * 5 interp_ref, 6 max_pb_part, 7 max_tb_part, 8 num_intra_modes, 9 size, 10 encode_this_size, 11 context index, 12 context cbp, 13 num_skip, 14 num_merge,
+ * 15 mvp.x, 16 mvp.y, 17 mode, 18 intra_mode, 19 skip_idx, 20 pb_part, 21 ref_idx0, 22 ref_idx1, 23 dir, 24 tb_param, 25 tb_split, 26..28 cbp y / u / v,
+ * 29..36 mv_arr0 (x, y), 37..44 mv_arr1.  max_delta_qp = bitrate = 0, 4:2:0; the frame is as large as the block or empty, which makes
+ * encode_this_size (enc/write_bits.c:386-388) come out as asked. */
+static enc_params syn_params;
+static encoder_info_t syn_ei;
+static block_info_t syn_bi;
+static block_context_t syn_ctx;
+static block_param_t syn_bp;
+static void syn_fill(const int* q) {
+  memset(&syn_params, 0, sizeof syn_params); memset(&syn_ei, 0, sizeof syn_ei); memset(&syn_bi, 0, sizeof syn_bi);
+  memset(&syn_ctx, 0, sizeof syn_ctx); memset(&syn_bp, 0, sizeof syn_bp);
+  syn_params.enable_bipred = q[4]; syn_params.subsample = 420; syn_params.log2_sb_size = 7;
+  syn_ei.params = &syn_params;
+  syn_ei.frame_info.frame_type = (frame_type_t)q[2]; syn_ei.frame_info.num_ref = q[3]; syn_ei.frame_info.interp_ref = q[5];
+  syn_ei.frame_info.num_intra_modes = q[8];
+  syn_ei.width = syn_ei.height = q[10] ? q[9] : 0;
+  syn_bi.block_pos.size = (uint8_t)q[9]; syn_bi.block_pos.bwidth = syn_bi.block_pos.bheight = (uint8_t)q[9]; syn_bi.block_pos.sb_size = 128;
+  syn_bi.block_context = &syn_ctx; syn_bi.sub = 1;
+  syn_ctx.index = (int8_t)q[11]; syn_ctx.cbp = (int8_t)q[12];
+  syn_bi.max_num_pb_part = q[6]; syn_bi.max_num_tb_part = q[7]; syn_bi.num_skip_vec = q[13]; syn_bi.num_merge_vec = q[14];
+  syn_bi.mvp.x = (int16_t)q[15]; syn_bi.mvp.y = (int16_t)q[16];
+  syn_bp.mode = (block_mode_t)q[17]; syn_bp.intra_mode = (intra_mode_t)q[18]; syn_bp.skip_idx = q[19]; syn_bp.pb_part = q[20];
+  syn_bp.ref_idx0 = q[21]; syn_bp.ref_idx1 = q[22]; syn_bp.dir = q[23]; syn_bp.tb_param = q[24]; syn_bp.tb_split = q[25];
+  syn_bp.cbp.y = (uint8_t)q[26]; syn_bp.cbp.u = (uint8_t)q[27]; syn_bp.cbp.v = (uint8_t)q[28];
+  for (int k = 0; k < 4; k++) {
+    syn_bp.mv_arr0[k].x = (int16_t)q[29 + 2 * k]; syn_bp.mv_arr0[k].y = (int16_t)q[30 + 2 * k];
+    syn_bp.mv_arr1[k].x = (int16_t)q[37 + 2 * k]; syn_bp.mv_arr1[k].y = (int16_t)q[38 + 2 * k];
+  }
+}
+/* write_super_mode (enc/write_bits.c:257-358) with split_flag = par[1], encode_this_size = par[10] */
+int ref_write_super_mode(const int* par, uint8_t* out, int out_bytes) {
+  stream_t s;
+  syn_fill(par);
+  syn_open(&s);
+  write_super_mode(&s, &syn_ei, &syn_bi, &syn_bp, par[1], par[10]);
+  return syn_close(&s, out, out_bytes);
+}
+/* write_block (enc/write_bits.c:360-600); cy / cu / cv: 4 * MAX_QUANT_SIZE^2 coefficients each, laid out as block_param_t holds them */
+int ref_write_block(const int* par, const int16_t* cy, const int16_t* cu, const int16_t* cv, uint8_t* out, int out_bytes) {
+  stream_t s;
+  syn_fill(par);
+  memcpy(syn_bp.coeff_y, cy, sizeof syn_bp.coeff_y); memcpy(syn_bp.coeff_u, cu, sizeof syn_bp.coeff_u); memcpy(syn_bp.coeff_v, cv, sizeof syn_bp.coeff_v);
+  syn_open(&s);
+  int r = write_block(&s, &syn_ei, &syn_bi, &syn_bp);
+  int n = syn_close(&s, out, out_bytes);
+  return r == n ? n : -1;
+}
+/* zigzag16 / zigzag64 / zigzag256 (common/common_tables.c): position -> scan index of a qsize x qsize block */
+void ref_zigzag(int qsize, int* out) {
+  const int* z = qsize == 4 ? zigzag16 : qsize == 8 ? zigzag64 : zigzag256;
+  for (int i = 0; i < qsize * qsize; i++) out[i] = z[i];
+}
 #endif

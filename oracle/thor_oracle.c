@@ -377,6 +377,7 @@ static int vlc_len(int n, unsigned cn) {
   if (n == 10) return 1 + 2 * ilog2(cn + 1);
   return cn == (unsigned)(n - 10) ? n - 10 : (int)cn + 1;
 }
+int orc_vlc_len(int n, unsigned cn) { return vlc_len(n, cn); }
 int orc_coeff_bits(const int16_t* coeff, int size, int type) {
   int q = size < 16 ? size : 16, N = q * q, zz[256], s[256], bits = 0;
   zigzag(q, zz);

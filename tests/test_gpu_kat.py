@@ -320,3 +320,82 @@ def test_early_skip_sub_block_tests_match_reference_kat():
     got = thor_amd.binding.kat_early_skip(arg[:, 0], K7['es_org'], K7['es_pred'], arg[:, 1], arg[:, 2], arg[:, 3] / 10.0, 8)
     bad = np.flatnonzero(got != want)
     assert not len(bad), (len(bad), [(int(i), arg[i].tolist(), int(got[i]), int(want[i])) for i in bad[:6]])
+
+
+# ---- the block syntax writer and its bit counter on the device (thor_amd/csrc/tk_bits.h through thor_hip_kat_coeff_syntax / thor_hip_kat_block_syntax, one launch
+# per test) against the reference's bit strings (tests/golden/gen_kat9.py -> kat9.npz), and k_gather_bits ---------------------------------------------------------
+def test_coeff_syntax_matches_reference_kat():
+    """write_coeff, every coefficient item of kat9.npz: coeff_bits_team<SP_LDS> and <SP_GLOBAL> (the 64-lane ballot automaton with its carries across rounds)
+    equal the reference length; bs_coeff on one lane and bs_coeff_team on 64 lanes (the readlane form that only exists on the device) write the reference
+    string at start offsets 0, 1, 31, 32, 33, 63, 17 and leave the bits before the offset as they were."""
+    import thor_amd
+    import kat_bits as B
+    want = B.strings('co')
+    n = len(want)
+    assert n >= 2000
+    par = np.zeros((n, 4), dtype=np.int32)
+    par[:, :2] = B.K9['co_par']; par[:, 2] = [(0, 1, 31, 32, 33, 63, 17)[i % 7] for i in range(n)]; par[:, 3] = B.CO_WORDS * 32
+    fill = np.full((n, B.CO_WORDS), B.FILL, dtype=np.uint32)
+    out, b1, bt = thor_amd.binding.kat_coeff_syntax(par, B.K9['co_coef'], B.CO_WORDS, fill, fill)
+    fill_bits = B.word_bits(fill[:1])[0]
+    bad = [f'coeff_bits_team item {i} (size {par[i, 0]} type {par[i, 1]}): {out[i, :2].tolist()} want {len(w)}' for i, w in enumerate(want) if not (out[i, 0] == out[i, 1] == len(w))]
+    bad += B.check_emitted('bs_coeff', B.word_bits(b1), out[:, 2], out[:, 3], want, par[:, 2], fill_bits)
+    bad += B.check_emitted('bs_coeff_team', B.word_bits(bt), out[:, 4], out[:, 5], want, par[:, 2], fill_bits)
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+
+
+def test_block_syntax_matches_reference_kat():
+    """write_block and write_super_mode, every item of kat9.npz, plus every recorded put_vlc codeword and write_mv string as items of their own: bs_block_head_t,
+    bs_block_t<false, SP_LDS / SP_GLOBAL> without and with ybits equal the reference length (SP_LDS: where the product keeps the chroma buffers in LDS), the
+    cooperative and the single-lane emission equal the reference string."""
+    import thor_amd
+    import kat_bits as B
+    rows, want, head = B.all_rows()
+    assert len(rows) >= 6000 and (rows[:, 0] == 0).sum() >= 1400 and ((rows[:, 0] == 0) & (rows[:, 25] == 1) & (rows[:, 9] >= 64)).sum() >= 40
+    out, bc, b1 = thor_amd.binding.kat_block_syntax(rows, B.K9['co_coef'], B.BL_WORDS, B.FILL)
+    bad = B.check_block_out(out, rows, want, head)
+    bad += B.check_emitted('cooperative emission', B.word_bits(bc), out[:, 5], out[:, 6], want)
+    bad += B.check_emitted('single-lane emission', B.word_bits(b1), out[:, 7], out[:, 8], want)
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+
+
+def test_gather_bits_matches_numpy_concatenation():
+    """k_gather_bits: 64 strings of 1 .. 3000 bits from an arbitrary first bit, most back to back (so string ends land mid-word and, for the strings sized to it, on
+    word boundaries), four after a gap of zero bits (7 bits, two whole words, 45 bits, up to a word boundary plus a word), the source words filled with set bits beyond nbits (the tail mask), against a numpy bit concatenation."""
+    import thor_amd
+    rng = np.random.default_rng(64)
+    nbits = rng.integers(1, 3001, 64)
+    nbits[:4] = (1, 31, 32, 3000)
+    pos, dst_bit = 13, []
+    for i in range(64):
+        if i % 5 == 4: nbits[i] += (-(pos + nbits[i])) % 32      # this string ends on a word boundary, the next one starts on it
+        pos += {10: 7, 20: 64, 30: 45, 40: 32 + (-pos) % 32}.get(i, 0)   # four strings start after a gap: a few bits, whole words, and onto a word boundary
+        dst_bit.append(pos); pos += int(nbits[i])
+    assert nbits.max() <= 3031 and sum((d + n) % 32 == 0 for d, n in zip(dst_bit, nbits)) >= 12
+    src_off = np.concatenate([[0], np.cumsum((nbits + 31) // 32)])
+    src = rng.integers(0, 1 << 32, int(src_off[-1]), dtype=np.uint64).astype(np.uint32)
+    sbits = np.unpackbits(src.astype('>u4').view(np.uint8))
+    want = np.zeros(32 * ((pos + 31) // 32 + 1), dtype=np.uint8)
+    for i in range(64):
+        o = 32 * int(src_off[i])
+        want[dst_bit[i]:dst_bit[i] + nbits[i]] = sbits[o:o + nbits[i]]
+        if nbits[i] % 32: src[src_off[i + 1] - 1] |= np.uint32((1 << (32 - nbits[i] % 32)) - 1)   # garbage behind the string in its last word
+    got = thor_amd.binding.kat_gather_bits(src, src_off[:-1], nbits, dst_bit, len(want) // 32)
+    gbits = np.unpackbits(got.astype('>u4').view(np.uint8))
+    assert np.array_equal(gbits, want), f'first differing bit {int(np.flatnonzero(gbits != want)[0])}'
+
+
+def test_engine_only_codewords_longer_than_32_bits():
+    """Engine-only property, no reference comparison: levels up to 32767 take the len > 32 branch of bs_vlc_t; emitted length = counted length, and the string is
+    len - k zeros followed by the k significant bits of the code (kat_bits.vlc_code), for bs_coeff and bs_coeff_team on the device."""
+    import thor_amd
+    import kat_bits as B
+    B.check_long_codewords(lambda par, coef, b1, bt: thor_amd.binding.kat_coeff_syntax(par, coef, B.CO_WORDS, b1, bt))
+
+
+def test_engine_only_overflow_keeps_position_and_canaries():
+    """Engine-only property: with a capacity shorter than the string ovf is set, pos still advances to the full length, and the words from the capacity on are
+    unchanged, for bs_coeff and bs_coeff_team on the device."""
+    import thor_amd
+    import kat_bits as B
+    B.check_overflow(lambda par, coef, b1, bt: thor_amd.binding.kat_coeff_syntax(par, coef, B.CO_WORDS, b1, bt))

@@ -163,3 +163,95 @@ def test_motion_search_host_build_matches_reference_kat(tmp_path):
         rep = me_report(got, want, par)
         assert rep is None, f'64-lane host team, bitdepth {bd}: {rep}'
     assert 150 <= total <= 200
+
+
+# ---- the block syntax writer and its bit counter (thor_amd/csrc/tk_bits.h) against the reference's bit strings (tests/golden/gen_kat9.py -> kat9.npz) --------------
+def build_bits_host(d, lanes):
+    so = str(d / ('kat_host_bits_l.so' if lanes else 'kat_host_bits.so'))
+    extra = ['-O2', '-DTHOR_HOSTSIM_LANES=64', '-pthread'] if lanes else ['-O1']
+    subprocess.check_call(['g++', '-std=c++17', '-fno-strict-aliasing', '-DTHOR_HOSTSIM', '-ffp-contract=off', '-shared', '-fPIC'] + extra + ['-o', so,
+                           os.path.join(ROOT, 'tests', 'hostsim', 'kat_host_bits.cpp')])
+    return C.CDLL(so)
+
+
+def bits_host_coeff(lib, lanes, start=None):
+    import kat_bits as B
+    par2, coef = B.K9['co_par'], np.ascontiguousarray(B.K9['co_coef'])
+    n = len(par2)
+    par = np.zeros((n, 4), dtype=np.int32)
+    par[:, :2] = par2; par[:, 2] = 0 if start is None else start; par[:, 3] = B.CO_WORDS * 32
+    b1 = np.full((n, B.CO_WORDS), B.FILL, dtype=np.uint32); bt = b1.copy()
+    out = np.full((n, 6), -7, dtype=np.int32)
+    assert lib.h_coeff_syntax(lanes, n, P(par), P(coef), B.CO_WORDS, P(b1), P(bt), P(out)) == 0
+    return out, b1, bt
+
+
+def bits_host_block(lib, lanes, rows):
+    import kat_bits as B
+    pool = np.ascontiguousarray(B.K9['co_coef'])
+    n = len(rows)
+    bc = np.full((n, B.BL_WORDS), B.FILL, dtype=np.uint32); b1 = bc.copy()
+    out = np.full((n, 10), -7, dtype=np.int32)
+    assert lib.h_block_syntax(lanes, n, P(rows), P(pool), len(pool), B.BL_WORDS, P(bc), P(b1), P(out)) == 0
+    return out, bc, b1
+
+
+def test_block_syntax_host_build_matches_reference_kat(tmp_path):
+    """Every item of kat9.npz against the 1-lane host build of tk_bits.h, bit-exact in length and string: put_vlc codewords (tables 0-8, 10-18 up to 31 bits),
+    write_mv, write_coeff (both emitters - on the host bs_coeff_team takes the serial loop - and both counts, at start offsets 0, 1, 31, 32, 33, 63, 17 with the
+    bits before the offset preserved), write_super_mode and write_block (bs_block_head_t, the counting instances without and with ybits, both emissions)."""
+    import kat_bits as B
+    L1 = build_bits_host(tmp_path, 0)
+    want = B.strings('co')
+    assert len(want) >= 2000
+    start = np.array([(0, 1, 31, 32, 33, 63, 17)[i % 7] for i in range(len(want))], dtype=np.int32)
+    out, b1, bt = bits_host_coeff(L1, 1, start)
+    fill_bits = B.word_bits(np.full((1, B.CO_WORDS), B.FILL, dtype=np.uint32))[0]
+    bad = [f'coeff_bits_team item {i}: {out[i, :2].tolist()} want {len(w)}' for i, w in enumerate(want) if not (out[i, 0] == out[i, 1] == len(w))]
+    bad += B.check_emitted('bs_coeff', B.word_bits(b1), out[:, 2], out[:, 3], want, start, fill_bits)
+    bad += B.check_emitted('bs_coeff_team', B.word_bits(bt), out[:, 4], out[:, 5], want, start, fill_bits)
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+    rows, bwant, head = B.all_rows()
+    assert len(rows) >= 6000
+    out, bc, b1 = bits_host_block(L1, 1, rows)
+    bad = B.check_block_out(out, rows, bwant, head)
+    bad += B.check_emitted('cooperative emission', B.word_bits(bc), out[:, 5], out[:, 6], bwant)
+    bad += B.check_emitted('single-lane emission', B.word_bits(b1), out[:, 7], out[:, 8], bwant)
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+
+
+@pytest.mark.parametrize('lanes', [8, 16, 64])
+def test_block_syntax_counts_host_lane_teams_match_reference_kat(tmp_path, lanes):
+    """coeff_bits_team's ballot automaton with W = 8, 16 and 64 positions per round (teams of OS threads, the widths of test_reference_golden.py) against the
+    reference's write_coeff lengths on every coefficient item of kat9.npz - levels 1..5 on either side of every round boundary, runs across them, the
+    trailing symbols at N - 1 / N - 2 - and the counting instances of bs_block_t on every block item."""
+    import kat_bits as B
+    L = build_bits_host(tmp_path, 1)
+    want = B.strings('co')
+    out, _, _ = bits_host_coeff(L, lanes)
+    bad = [f'coeff_bits_team W={lanes} item {i} (size {B.K9["co_par"][i][0]} type {B.K9["co_par"][i][1]}): {out[i, :2].tolist()} want {len(w)}'
+           for i, w in enumerate(want) if not (out[i, 0] == out[i, 1] == len(w))]
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+    sel = np.flatnonzero(B.K9['bl_par'][:, 0] == 0)
+    allw = B.strings('bl')
+    rows, bwant, head = np.ascontiguousarray(B.K9['bl_par'][sel]), [allw[i] for i in sel], B.K9['bl_head'][sel]
+    out, _, _ = bits_host_block(L, lanes, rows)
+    bad = B.check_block_out(out, rows, bwant, head)
+    assert not bad, f'{len(bad)} failures:\n' + '\n'.join(bad[:8])
+
+
+def test_block_syntax_engine_only_long_codewords_and_overflow_host_build(tmp_path):
+    """Two properties of the engine's bit sink that have no reference answer (the reference's putbits is undefined from 32 bits; it has no capacity check):
+    codewords longer than 32 bits (levels up to 32767, the len > 32 branch of bs_vlc_t) come out as len - k zeros and the k significant bits of the code, and
+    the counted length agrees; with a capacity shorter than the string ovf is set, pos still advances to the full length and no word from the capacity on is
+    written."""
+    import kat_bits as B
+    L1 = build_bits_host(tmp_path, 0)
+
+    def run(par, coef, b1, bt):
+        par, coef = np.ascontiguousarray(par, dtype=np.int32), np.ascontiguousarray(coef, dtype=np.int16)
+        out = np.full((len(par), 6), -7, dtype=np.int32)
+        assert L1.h_coeff_syntax(1, len(par), P(par), P(coef), B.CO_WORDS, P(b1), P(bt), P(out)) == 0
+        return out, b1, bt
+    B.check_long_codewords(run)
+    B.check_overflow(run)

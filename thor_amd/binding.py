@@ -14,11 +14,11 @@ def lib_path():
 
 
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-strict-aliasing', '-fPIC', '-pthread']
-NATIVE_SOURCES = ['thor_hip.cpp', 'thor_hip_lat.cpp', 'thor_hip_wide.cpp']   # the throughput build of the engine (with its hip_*.h parts) + its two builds for the few-stream operating points
+NATIVE_SOURCES = ['thor_hip.cpp', 'thor_hip_lat.cpp', 'thor_hip_wide.cpp', 'thor_hip_katbits.cpp']   # the throughput build of the engine (with its hip_*.h parts) + its two builds for the few-stream operating points + the known-answer kernels of the block syntax
 
 
 def build_native(force=False):
-    """Compile libthor_hip.so (gfx950) and the C front end in-tree with hipcc/gcc: the two translation units are compiled side by side, then linked."""
+    """Compile libthor_hip.so (gfx950) and the C front end in-tree with hipcc/gcc: the translation units are compiled side by side, then linked."""
     csrc = os.path.join(REPO_ROOT, 'thor_amd', 'csrc')
     out = os.path.join(REPO_ROOT, 'thor_amd', 'libthor_hip.so')
     hdrs = [os.path.join(csrc, f) for f in os.listdir(csrc)]
@@ -467,6 +467,39 @@ def kat_early_skip(chroma, org, pred, size, qp, thr, bitdepth=8):
     out = np.full(n, -1, dtype=np.int32)
     _kat('thor_hip_kat_early_skip', _vp(chroma), _vp(org), _vp(pred), _vp(size), _vp(qp), _vp(thr), bitdepth, n, _vp(out))
     return out
+
+
+def kat_coeff_syntax(par, coef, words, buf_single, buf_team):
+    """thor_hip_kat_coeff_syntax: par (n, 4) size, type, start bit, capacity; coef (n, 256); buf_* (n, words) uint32, pre-filled.  Returns (out (n, 6),
+    buf_single, buf_team) - the buffers as the device left them."""
+    par = np.ascontiguousarray(par, dtype=np.int32); coef = np.ascontiguousarray(coef, dtype=np.int16)
+    n = len(par)
+    b1 = np.ascontiguousarray(buf_single, dtype=np.uint32).copy(); bt = np.ascontiguousarray(buf_team, dtype=np.uint32).copy()
+    assert par.shape == (n, 4) and coef.shape == (n, 256) and b1.shape == (n, words) and bt.shape == (n, words)
+    out = np.zeros((n, 6), dtype=np.int32)
+    _kat('thor_hip_kat_coeff_syntax', n, _vp(par), _vp(coef), words, _vp(b1), _vp(bt), _vp(out))
+    return out, b1, bt
+
+
+def kat_block_syntax(par, pool, words, fill=0):
+    """thor_hip_kat_block_syntax: par (n, 57) rows (thor_amd/csrc/tk_kat_bits.h), pool (npool, 256) coefficients.  Returns (out (n, 10), buf_coop, buf_single),
+    the buffers (n, words) uint32 pre-filled with `fill`."""
+    par = np.ascontiguousarray(par, dtype=np.int32); pool = np.ascontiguousarray(pool, dtype=np.int16)
+    n = len(par)
+    assert par.shape == (n, 57) and pool.ndim == 2 and pool.shape[1] == 256
+    bc = np.full((n, words), fill, dtype=np.uint32); b1 = np.full((n, words), fill, dtype=np.uint32)
+    out = np.zeros((n, 10), dtype=np.int32)
+    _kat('thor_hip_kat_block_syntax', n, _vp(par), _vp(pool), len(pool), words, _vp(bc), _vp(b1), _vp(out))
+    return out, bc, b1
+
+
+def kat_gather_bits(src, src_off, nbits, dst_bit, dst_words):
+    """thor_hip_kat_gather_bits: strings of nbits[i] bits at word src_off[i] of `src` to bit dst_bit[i] of a zeroed destination; returns it (uint32)."""
+    src = np.ascontiguousarray(src, dtype=np.uint32); src_off = np.ascontiguousarray(src_off, dtype=np.int32)
+    nbits = np.ascontiguousarray(nbits, dtype=np.int32); dst_bit = np.ascontiguousarray(dst_bit, dtype=np.int64)
+    dst = np.zeros(dst_words, dtype=np.uint32)
+    _kat('thor_hip_kat_gather_bits', len(nbits), _vp(src), len(src), _vp(src_off), _vp(nbits), _vp(dst_bit), _vp(dst), dst_words)
+    return dst
 
 
 def frame_sse(a, b, width, height, bitdepth=8):

@@ -34,7 +34,7 @@ static bool ensure_init(int device) {
   static Tables h;
   init_tables(&h);
   HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_tab), &h, sizeof(h)));
-  if (thor_lat_upload_tables(&h, sizeof(h)) || thor_wide_upload_tables(&h, sizeof(h))) { fprintf(stderr, "Run-time error...\nthor_hip: table upload of the few-stream kernels failed\n...now exiting to system...\n"); abort(); }
+  if (thor_lat_upload_tables(&h, sizeof(h)) || thor_wide_upload_tables(&h, sizeof(h)) || thor_katbits_upload_tables(&h, sizeof(h))) { fprintf(stderr, "Run-time error...\nthor_hip: table upload of the other translation units (few-stream kernels, block-syntax test kernels) failed\n...now exiting to system...\n"); abort(); }
   g_inited = true;
   return true;
 }

@@ -1,6 +1,7 @@
 // hip_kat.h - C ABI, kernel-level batch entry points for the known-answer tests ("KAT"), and thor_hip_superblock_kernel_info / _in_use (part of the
 // translation unit thor_hip.cpp: the kernels here run the very device functions the superblock kernel calls).
 #pragma once
+#include "tk_kat_bits.h"
 namespace tk {
 // The kernels behind the known-answer entry points run the product's device code on one block / transform unit per workgroup of
 // one wavefront; PIX = uint8_t (the reference's _lbd functions) or uint16_t (_hbd, bitdepth 9..12).
@@ -554,6 +555,50 @@ extern "C" int thor_hip_kat_motion_estimate_bi(const void* cur, const void* ref0
 extern "C" int thor_hip_kat_early_skip(const int* chroma, const void* org, const void* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out) {
   KAT_BD(kat_early_skip<uint8_t>(chroma, (const uint8_t*)org, (const uint8_t*)pred, size, qp, thr, 8, n, out),
          kat_early_skip<uint16_t>(chroma, (const uint16_t*)org, (const uint16_t*)pred, size, qp, thr, bitdepth, n, out));
+}
+// ---- the block syntax (tk_bits.h) against the reference's bit strings: tests/golden/gen_kat9.py -> kat9.npz.  The two kernels live in a translation unit of
+// their own (thor_hip_katbits.cpp says why); k_gather_bits is the throughput build's ------------------------------------------------------------------------
+extern "C" int thor_hip_kat_coeff_syntax(int n, const int* par, const int16_t* coef, int words, uint32_t* buf_single, uint32_t* buf_team, int* out) {
+  if (n <= 0 || !par || !coef || words <= 0 || words > (1 << 16) || !buf_single || !buf_team || !out) return 1;
+  for (int i = 0; i < n; i++) if (kat_coeff_check(par + kKatCoPar * i, words)) return 1;
+  if (!ensure_init_any()) return 3;
+  DevBuf<int> d_par((size_t)kKatCoPar * n, par), d_o((size_t)kKatCoOut * n);
+  DevBuf<int16_t> d_c((size_t)256 * n, coef);
+  DevBuf<uint32_t> d_1((size_t)words * n, buf_single), d_t((size_t)words * n, buf_team);
+  if (thor_katbits_launch_coeff(g_stream, n, d_par, d_c, words, d_1, d_t, d_o)) return 3;
+  backend::d2h(buf_single, d_1, (size_t)words * n * 4); backend::d2h(buf_team, d_t, (size_t)words * n * 4);
+  backend::d2h(out, d_o, (size_t)kKatCoOut * n * 4);
+  return 0;
+}
+extern "C" int thor_hip_kat_block_syntax(int n, const int* par, const int16_t* pool, int npool, int words, uint32_t* buf_coop, uint32_t* buf_single, int* out) {
+  if (n <= 0 || !par || npool < 0 || (npool && !pool) || words <= 0 || words > (1 << 16) || !buf_coop || !buf_single || !out) return 1;
+  std::vector<int16_t> coef((size_t)n * 3072);
+  for (int i = 0; i < n; i++) if (kat_block_resolve(par + kKatBlPar * i, pool, npool, coef.data() + (size_t)i * 3072)) return 1;
+  if (!ensure_init_any()) return 3;
+  DevBuf<int> d_par((size_t)kKatBlPar * n, par), d_o((size_t)kKatBlOut * n);
+  DevBuf<int16_t> d_c(coef.size(), coef.data());
+  DevBuf<uint32_t> d_w((size_t)words * n, buf_coop), d_1((size_t)words * n, buf_single);
+  if (thor_katbits_launch_block(g_stream, n, d_par, d_c, words, d_w, d_1, d_o)) return 3;
+  backend::d2h(buf_coop, d_w, (size_t)words * n * 4); backend::d2h(buf_single, d_1, (size_t)words * n * 4);
+  backend::d2h(out, d_o, (size_t)kKatBlOut * n * 4);
+  return 0;
+}
+extern "C" int thor_hip_kat_gather_bits(int n, const uint32_t* src, int src_words, const int* src_off, const int* nbits, const long long* dst_bit, uint32_t* dst, int dst_words) {
+  if (n <= 0 || !src || src_words <= 0 || !src_off || !nbits || !dst_bit || !dst || dst_words <= 0) return 1;
+  for (int i = 0; i < n; i++) {
+    if (nbits[i] < 0 || src_off[i] < 0 || dst_bit[i] < 0) return 1;
+    if ((long long)src_off[i] + (nbits[i] + 31) / 32 > src_words || dst_bit[i] + nbits[i] > (long long)dst_words * 32) return 2;
+  }
+  if (!ensure_init_any()) return 3;
+  std::vector<backend::GatherItem> items(n);
+  DevBuf<uint32_t> d_src((size_t)src_words, src), d_dst((size_t)dst_words);   // destination zeroed (dev_alloc clears)
+  for (int i = 0; i < n; i++) {
+    items[i].src = d_src.get() + src_off[i]; items[i].nbits = nbits[i]; items[i].dst_bit = dst_bit[i];
+  }
+  DevBuf<backend::GatherItem> d_items((size_t)n, items.data());
+  backend::run_gather(d_items, n, d_dst);
+  backend::d2h(dst, d_dst, (size_t)dst_words * 4);
+  return 0;
 }
 // Per-plane SSE of two host frames through k_frame_sse (the kernel the engine launches with frame distortion on).
 template <typename PIX> int frame_sse_host(const PIX* a, const PIX* b, int width, int height, unsigned long long out[3]) {

@@ -9,7 +9,7 @@
 //   hip_backend.h   device initialisation, namespace backend (memory, scheduler state, every run_* launch sequence), host <-> device helpers
 //   hip_abi_seq.h   the sequence API of include/thor_hip.h
 //   hip_abi_seam.h  the drop-in seam of include/thor_abi.h (encode_frame_lbd / _hbd)
-//   hip_kat.h       the known-answer kernels and their entry points, thor_hip_superblock_kernel_info / _in_use
+//   hip_kat.h       the known-answer kernels and their entry points (the two block-syntax kernels: thor_hip_katbits.cpp), thor_hip_superblock_kernel_info / _in_use
 // The order of the includes is the order in which kernels are defined and templates instantiated, i.e. the order of the code object: keep it.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -49,6 +49,10 @@
   extern "C" __attribute__((visibility("hidden"))) int P##launch_u8(int wgs, void* stream, const void* jobs, const void* dfargs, size_t dfargs_bytes, size_t job_bytes, size_t slot_bytes);
 TK_ALT_DECLS(thor_lat_)    // thor_hip_lat.cpp: 256 VGPRs, two four-wave workgroups per CU
 TK_ALT_DECLS(thor_wide_)   // thor_hip_wide.cpp: eight-wave workgroups, one per CU
+// thor_hip_katbits.cpp: the known-answer kernels of the block syntax (device pointers throughout)
+extern "C" __attribute__((visibility("hidden"))) int thor_katbits_upload_tables(const void* tables, size_t bytes);
+extern "C" __attribute__((visibility("hidden"))) int thor_katbits_launch_coeff(void* stream, int n, const int* par, const int16_t* coef, int words, uint32_t* buf_single, uint32_t* buf_team, int* out);
+extern "C" __attribute__((visibility("hidden"))) int thor_katbits_launch_block(void* stream, int n, const int* par, const int16_t* coef, int words, uint32_t* buf_coop, uint32_t* buf_single, int* out);
 
 
 namespace tk {
