@@ -55,6 +55,7 @@ typedef struct thor_hip_params { /* the enc_params fields this path honours (enc
   int dqpB, dqpB0, dqpB1, dqpB2, dqpB3;
   float mqpB, mqpB0, mqpB1, mqpB2, mqpB3;
   int max_clpf_strength; /* CLPF strength cap (enc/strings.c:351) */
+  int log2_sb_size;      /* 7: 128x128 superblocks (the default), 6: 64x64; nothing else is accepted (enc/strings.c:299) */
 } thor_hip_params;
 
 typedef struct thor_hip_encoder thor_hip_encoder;
@@ -67,8 +68,14 @@ int thor_hip_params_from_config(thor_hip_params* p, const char* cfg_path);
  * honoured; 1 = not an option of the reference's table; 2 = known, but the value is not implemented by this path
  * (quantisation matrices, delta-QP / rate control, sync, subsampling other than 4:2:0, SB size other than 128: they
  * change the bitstream, so they are rejected instead of ignored); 3 = front-end option (-if/-of/-rf/-n/-skip).
- * thor_hip_params_from_config applies the same rule to every token of the file (returns non-zero). */
+ * thor_hip_params_from_config applies the same rule to every token of the file (returns non-zero), except that a file
+ * may say "-log2_sb_size 6". */
 int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value);
+
+/* Choose the superblock size: log2_sb_size 7 (128x128) or 6 (64x64) is stored in *p and 0 returned; any other value
+ * returns 2 and leaves *p alone.  thor_hip_params_set keeps answering 2 to "-log2_sb_size" with anything but 7, as it
+ * did before 64x64 superblocks were implemented, so this is the call (or the struct field itself) to select them. */
+int thor_hip_params_set_sb_size(thor_hip_params* p, int log2_sb_size);
 
 int thor_hip_device_count(void);
 /* One process drives ONE GPU from ONE thread (the reference's encode_frame is neither re-entrant nor threaded,

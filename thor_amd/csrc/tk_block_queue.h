@@ -463,7 +463,7 @@ TK_MDW unsigned mode_decision_par(const Wg wg, const Team t, JobR<PIX> J, WsP<PI
   const int inter = J.frame_type != F_I;
   TK_PROFMD_MARK(pqs_);
   mv_t mvp = mk_mv(0, 0);
-  if (inter) mvp = get_mv_pred(J.cells, J.cell_stride, nd->ypos, nd->xpos, c.width, c.height, nd->size, kMaxSb);
+  if (inter) mvp = get_mv_pred(J.cells, J.cell_stride, nd->ypos, nd->xpos, c.width, c.height, nd->size, sb_size_of(c));
   t.sync();
   if (t.rank == 0) {
     int n = 0;

@@ -353,8 +353,8 @@ TK_DEVNI int encode_block(const Team t, JobR<PIX> J, WsP<PIX> ws, Node& nd_, Blk
   int cbp_y = 0, cbp_u = 0, cbp_v = 0;
 
   if (TKU(p.mode) == M_INTRA) {
-    const int ur = upright_avail(nd.ypos, nd.xpos, size, size, c.width, kMaxSb);
-    const int dl = downleft_avail(nd.ypos, nd.xpos, size, size, c.height, kMaxSb);
+    const int ur = upright_avail(nd.ypos, nd.xpos, size, size, c.width, sb_size_of(c));
+    const int dl = downleft_avail(nd.ypos, nd.xpos, size, size, c.height, sb_size_of(c));
     const PIX* fy = J.rec.y + nd.ypos * J.rec.sy + nd.xpos;
     const PIX* fu = J.rec.u + yc * J.rec.sc + xc;
     const PIX* fv = J.rec.v + yc * J.rec.sc + xc;

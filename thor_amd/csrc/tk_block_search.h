@@ -160,8 +160,8 @@ template <typename PIX, int SP>
 TK_DEVNI unsigned intra_sad_search(const Team t, JobR<PIX> J, WsP<PIX> ws, const Node& nd, int num_modes, int* mode_out) {
   const auto& c = J.cfg;
   const int size = nd.size, bd = c.bitdepth;
-  const int ur = upright_avail(nd.ypos, nd.xpos, size, size, c.width, kMaxSb);
-  const int dl = downleft_avail(nd.ypos, nd.xpos, size, size, c.height, kMaxSb);
+  const int ur = upright_avail(nd.ypos, nd.xpos, size, size, c.width, sb_size_of(c));
+  const int dl = downleft_avail(nd.ypos, nd.xpos, size, size, c.height, sb_size_of(c));
   const PIX* fy = J.rec.y + nd.ypos * J.rec.sy + nd.xpos;
   const PIX* oy = ws->org_y;
   const int osy = ws->org_sy;

@@ -100,10 +100,16 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
     else if (k == "-enable_cfl_inter") p.cfl_inter = I();
     else if (k == "-bitdepth") p.bitdepth = I();
     else if (k == "-input_bitdepth") p.input_bitdepth = I();
+    else if (k == "-log2_sb_size") {
+      // 64x64 or 128x128 superblocks.  The reference's own range check (enc/strings.c:527) compares against MAX_SB_SIZE instead of its
+      // logarithm and lets 8 and more through into buffers sized for 128; here everything but 6 and 7 is refused.
+      p.log2_sb_size = I();
+      if (p.log2_sb_size != 6 && p.log2_sb_size != 7 && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
     else {
       // the rest of the reference's table: harmless at their defaults (or never read by the block path), fatal otherwise
       struct Opt { const char* name; const char* dflt; };  // dflt == nullptr: any value is fine (I/O and reporting options)
-      static const Opt rest[] = {{"-ph", "0"}, {"-fh", "0"}, {"-log2_sb_size", "7"},
+      static const Opt rest[] = {{"-ph", "0"}, {"-fh", "0"},
                                  {"-max_delta_qp", "0"}, {"-delta_qp_step", nullptr}, {"-sync", "0"}, {"-bitrate", "0"},
                                  {"-max_qp", nullptr}, {"-min_qp", nullptr}, {"-max_qpI", nullptr}, {"-min_qpI", nullptr},
                                  {"-qmtx", "0"}, {"-qmtx_offset", nullptr}, {"-subsample", "420"}, {"-frame_bitdepth", nullptr}};

@@ -713,7 +713,7 @@ TK_DEV int sat_pix(int v, int bitdepth) { return clampi(v, 0, (1 << bitdepth) - 
 // ---------------------------------------------------------------------------------
 // Codec constants (reference: common/global.h:54-93).
 // ---------------------------------------------------------------------------------
-enum { kMaxSb = 128, kMinBlk = 8, kMinPb = 4, kMaxQuant = 16, kPadY = 160, kMaxRefs = 4 };
+enum { kMaxSb = 128, kLog2MaxSb = 7, kMinBlk = 8, kMinPb = 4, kMaxQuant = 16, kPadY = 160, kMaxRefs = 4 };
 enum { F_I = 0, F_P = 1, F_B = 2 };
 enum { M_SKIP = 0, M_INTRA = 1, M_INTER = 2, M_BIPRED = 3, M_MERGE = 4 };
 enum { P_NONE = 0, P_HOR = 1, P_VER = 2, P_QUAD = 3 };
@@ -804,7 +804,17 @@ struct EncCfg {  // the subset of enc_params the block path reads (enc/mainenc.h
   int cfl_intra, cfl_inter;
   int max_num_ref, interp_ref_cfg;
   float early_skip_thr;
+  // kLog2MaxSb - enc_params::log2_sb_size: 0 = 128x128 superblocks, 1 = 64x64.  Stored as the distance from the compile-time maximum so that
+  // a zero-filled job (the known-answer kernels build theirs field by field) means the default size.
+  int sb_shift;
 };
+// The superblock size of the job's sequence (the reference's 1 << params->log2_sb_size): one LDS read of a wave-uniform word wherever
+// it is needed - no copy is carried through the block decisions.  kMaxSb stays the bound of every buffer (the reference's MAX_SB_SIZE).
+static_assert(kMaxSb == 1 << kLog2MaxSb, "kLog2MaxSb");
+TK_DEV int sb_size_of(const EncCfg& c) { return kMaxSb >> c.sb_shift; }
+#if !TK_HOST
+TK_DEV int sb_size_of(const TK_LDS EncCfg& c) { return kMaxSb >> __builtin_amdgcn_readfirstlane(c.sb_shift); }
+#endif
 
 template <typename PIX> struct FrameJob {
   EncCfg cfg;

@@ -382,7 +382,11 @@ template <typename PIX> class Engine {
  public:
   SeqParams sp;
   int S = 0, sb_cols = 0, sb_rows = 0, nsb = 0, max_diag = 0, ring_size = 0;
+  // Bit buffer of one 128x128 superblock: 2^19 bits for 24576 samples (4:2:0), 21.3 bits per sample.  The buffer of a smaller superblock
+  // (sb_words) is its share by area: the same bound per sample, which is what the worst case follows (the split flags and block headers of a
+  // 64x64 superblock are a quarter of those of a 128x128 one, its coefficients too).  The overflow check of finish_frames stays the guard.
   static const int kSbWords = 16384;
+  int sb_words = kSbWords;
   std::vector<Stream<PIX>> st;
   FrameJob<PIX>* d_jobs = nullptr;
   std::vector<FrameJob<PIX>> h_jobs;
@@ -406,7 +410,11 @@ template <typename PIX> class Engine {
 
   void open(const SeqParams& p, int num_streams) {
     sp = p; S = num_streams;
-    sb_cols = (p.width + kMaxSb - 1) / kMaxSb; sb_rows = (p.height + kMaxSb - 1) / kMaxSb; nsb = sb_cols * sb_rows;
+    // the superblock grid (encode_frame.c:642-644); open() is only reached with log2_sb_size 6 or 7 (tk_cli.h, hip_abi_seq.h:unsupported)
+    const int sb_size = 1 << p.log2_sb_size, sb_shift = kLog2MaxSb - p.log2_sb_size;
+    if (sb_shift < 0 || sb_shift > 1) { fprintf(stderr, "Run-time error...\nthor_hip: log2_sb_size must be 6 or 7\n...now exiting to system...\n"); abort(); }
+    sb_cols = (p.width + sb_size - 1) / sb_size; sb_rows = (p.height + sb_size - 1) / sb_size; nsb = sb_cols * sb_rows;
+    sb_words = kSbWords >> (2 * sb_shift);
     max_diag = 0;
     for (int t = 0; t <= (sb_cols - 1) + 2 * (sb_rows - 1); t++) {
       int n = 0;
@@ -451,7 +459,7 @@ template <typename PIX> class Engine {
       }
       s.cells = (DbCell*)backend::dev_alloc((size_t)cw * chh * sizeof(DbCell));
       backend::dev_memset(s.cells, 0, (size_t)cw * chh * sizeof(DbCell));
-      s.sb_bits = (uint32_t*)backend::dev_alloc((size_t)nsb * kSbWords * 4);
+      s.sb_bits = (uint32_t*)backend::dev_alloc((size_t)nsb * sb_words * 4);
       s.scratch = (uint8_t*)backend::dev_alloc(ws_bytes * max_diag);
       const int nfb = nfb_h * nfb_v;
       s.cdef_dir = (int8_t*)backend::dev_alloc((size_t)(p.width / 8) * (p.height / 8));
@@ -682,7 +690,7 @@ template <typename PIX> class Engine {
       c.enable_tb_split = sp.enable_tb_split; c.enable_pb_split = sp.enable_pb_split; c.enable_bipred = sp.enable_bipred;
       c.encoder_speed = sp.encoder_speed; c.intra_rdo = sp.intra_rdo; c.use_block_contexts = sp.use_block_contexts;
       c.cfl_intra = sp.cfl_intra; c.cfl_inter = sp.cfl_inter; c.max_num_ref = sp.max_num_ref; c.interp_ref_cfg = sp.interp_ref;
-      c.early_skip_thr = sp.early_skip_thr;
+      c.early_skip_thr = sp.early_skip_thr; c.sb_shift = kLog2MaxSb - sp.log2_sb_size;
       J.frame_type = f.frame_type; J.qp = f.qp; J.num_ref = f.num_ref; J.frame_num = f.frame_num;
       J.interp_ref = f.interp_ref; J.num_intra_modes = f.num_intra_modes;
       J.lambda = f.lambda_coeff * kSquaredLambdaQP[f.qp];
@@ -696,7 +704,7 @@ template <typename PIX> class Engine {
       }
       J.cells = q.cells; J.cell_stride = sp.width / 4;
       J.sb_cols = sb_cols; J.sb_rows = sb_rows;
-      J.sb_bits = q.sb_bits; J.sb_words = kSbWords; J.sb_nbits = q.sb_nbits; J.sb_status = q.sb_status;
+      J.sb_bits = q.sb_bits; J.sb_words = sb_words; J.sb_nbits = q.sb_nbits; J.sb_status = q.sb_status;
       J.scratch = q.scratch; J.scratch_bytes = ws_bytes;
       J.prof = d_prof;
       J.stats = d_stats;
@@ -820,7 +828,7 @@ template <typename PIX> class Engine {
         for (int i = 0; i < nsb; i++) {
           if (stt[(size_t)s * nsb + i]) { fprintf(stderr, "Run-time error...\nthor_hip: superblock %d bit buffer overflow\n...now exiting to system...\n", i); abort(); }
           backend::GatherItem& g = items[(size_t)s * nsb + i];
-          g.src = st[s].sb_bits + (size_t)i * kSbWords; g.nbits = nb[(size_t)s * nsb + i]; g.dst_bit = pos;
+          g.src = st[s].sb_bits + (size_t)i * sb_words; g.nbits = nb[(size_t)s * nsb + i]; g.dst_bit = pos;
           pos += g.nbits;
         }
         pos = (pos + 31) & ~31ll;  // streams start word aligned

@@ -7,6 +7,8 @@
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
  * S > 1 every stream's, in stream order, each after a line "stream <s>" - then the throughput line.  -stat appends the reference's
  * summary line of every stream to the file.
+ * THOR_STAGGER=1 in the environment (S > 1): the streams are coded in two groups half a frame apart (thor_hip_encode_staged_run) instead of
+ * frame by frame in lock step; the files written are the same.
  * All input frames are staged in HBM first; the timed region covers the encode loop only. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +20,18 @@ static double now_s(void) {
   struct timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return ts.tv_sec + 1e-9 * ts.tv_nsec;
+}
+
+/* thor_hip_encode_staged_run's callback: keep the reconstructions of the frames that just completed (display order) */
+struct done_ctx { thor_hip_encoder* e; unsigned char** recs; FILE** fr; int n; size_t fsz; };
+static void frames_done(void* user, int first, int count) {
+  struct done_ctx* c = (struct done_ctx*)user;
+  for (int s = first; s < first + count; s++)
+    if (c->fr[s]) {
+      unsigned char* r = (unsigned char*)malloc(c->fsz);
+      thor_hip_get_recon(c->e, s, r);
+      c->recs[(size_t)s * c->n + thor_hip_last_display_index(c->e, s)] = r;
+    }
 }
 
 int main(int argc, char** argv) {
@@ -41,7 +55,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-snrcalc")) snrcalc = atoi(v);
     else if (!strcmp(k, "-stat")) statf = v;
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
-    else if (thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
+    else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
   if (!inf) { fprintf(stderr, "usage: %s -cf cfg -if in.yuv -width W -height H -qp Q -n N ...\n", argv[0]); return 2; }
   FILE* fi = fopen(inf, "rb");
@@ -73,6 +87,13 @@ int main(int argc, char** argv) {
   unsigned char** recs = (unsigned char**)calloc((size_t)S * n, sizeof(unsigned char*));
   double t0 = now_s(), tenc = 0;
   int coded = 0;
+  if (S > 1 && getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER"))) {
+    struct done_ctx ctx = {e, recs, fr, n, fsz};
+    double a = now_s();
+    if (thor_hip_encode_staged_run(e, n, frames_done, &ctx)) { fprintf(stderr, "encode failed\n"); return 5; }
+    tenc = now_s() - a;
+    coded = n;
+  } else
   for (;;) {
     int active = 0;
     for (int s = 0; s < S; s++) active += thor_hip_next_frame(e, s, &slots[s]);
