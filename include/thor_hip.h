@@ -80,8 +80,8 @@ int thor_hip_params_set_sb_size(thor_hip_params* p, int log2_sb_size);
 int thor_hip_device_count(void);
 /* One process drives ONE GPU from ONE thread (the reference's encode_frame is neither re-entrant nor threaded,
  * SURVEY.md 8b): the first thor_hip_open binds the process to `device`; NULL is returned - with a message on stderr -
- * for a device index the node does not have, for a second device in the same process, and for parameter sets this
- * path cannot encode bit-exactly.  Multi-GPU = one process per GPU (bench.py under torch.distributed.run). */
+ * for a device index the node does not have (a node without any device included), for a second device in the same
+ * process, and for parameter sets this path cannot encode bit-exactly.  Multi-GPU = one process per GPU (bench.py under torch.distributed.run). */
 thor_hip_encoder* thor_hip_open(const thor_hip_params* p, int num_streams, int device);
 void thor_hip_close(thor_hip_encoder* e);
 
@@ -94,13 +94,20 @@ void thor_hip_close(thor_hip_encoder* e);
 int thor_hip_begin_sequence(thor_hip_encoder* e, int stream, int skip, int num_frames, int file_frames);
 int thor_hip_next_frame(thor_hip_encoder* e, int stream, int* display_index);
 
-/* Copy one planar 4:2:0 frame (bitdepth 8: bytes; >8: little-endian uint16) of stream `stream`
- * into HBM staging slot `slot` (slots are allocated on demand). */
+/* Frames cross this API at the INPUT bit depth: planar 4:2:0, input_bitdepth 8: bytes; 10 / 12: little-endian uint16 -
+ * thor_hip_frame_bytes(e) bytes each.  bitdepth (the depth the encoder works at) may be higher: (10, 8), (12, 8) and (12, 10) are
+ * accepted besides the three equal pairs.  The device then widens a staged frame (v << (bitdepth - input_bitdepth)) and rounds a
+ * reconstruction back (saturate((v + half) >> shift)), as the reference reads its -if and writes its -rf file
+ * (common/common_frame.c:484-650), and distortion is measured at the input depth (common/snr.c:39-61).  With equal depths nothing
+ * is launched or copied beyond what equal depths always took.  input_bitdepth > bitdepth is refused by thor_hip_open. */
+size_t thor_hip_frame_bytes(const thor_hip_encoder* e);
+/* Copy one such frame of stream `stream` into HBM staging slot `slot` (slots are allocated on demand). */
 int thor_hip_stage_frame(thor_hip_encoder* e, int stream, int slot, const void* yuv);
 /* Same, for a frame that is already in HBM (`dev_yuv` is a device pointer to the same contiguous planar layout):
  * device-to-device copy on the library's stream, synchronous at return.  The caller must have finished writing the
  * source (e.g. torch.cuda.synchronize()).  Used by bench.py: rank 0 broadcasts the clip over RCCL and every rank cuts
- * its chunks' frames out of it without a host round trip. */
+ * its chunks' frames out of it without a host round trip.  With input_bitdepth < bitdepth the widening kernel reads dev_yuv
+ * directly (no intermediate copy); dev_yuv must then be 16-byte aligned (returns 1 otherwise). */
 int thor_hip_stage_frame_device(thor_hip_encoder* e, int stream, int slot, const void* dev_yuv);
 /* Encode the next frame of every stream from staging slot slots[stream] (inputs already resident
  * in HBM).  Blocks until the bits of all streams are assembled on the host. */
@@ -128,7 +135,7 @@ int thor_hip_encode_frame(thor_hip_encoder* e, const void* const* yuv_per_stream
 size_t thor_hip_stream_bytes(const thor_hip_encoder* e, int stream);
 const uint8_t* thor_hip_stream_data(const thor_hip_encoder* e, int stream);
 /* Reconstruction of the most recently CODED frame of a stream (the reference writes these with -rf in
- * display order). */
+ * display order), thor_hip_frame_bytes(e) bytes of input-depth samples. */
 int thor_hip_get_recon(thor_hip_encoder* e, int stream, void* yuv_out);
 
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
@@ -154,8 +161,8 @@ typedef struct thor_hip_frame_stats {
   int ref_array[4];           /* window indices as coded; -1 = the interpolated frame, built from the next two entries */
   int ref_frame_num[4];       /* chunk-relative frame number of the frame each ref_array entry points at (-1 for the -1 entry) */
   int has_sse;                /* 1 when the frame's distortion was measured */
-  unsigned long long sse[3];  /* Y, U, V: exact sums of squared differences */
-  double psnr[3];             /* snr_yuv's formula on sse (common/snr.c:32-99); inf when sse == 0; 0 when not measured */
+  unsigned long long sse[3];  /* Y, U, V: exact sums of squared differences, at the input bit depth */
+  double psnr[3];             /* snr_yuv's formula on sse (common/snr.c:32-99), maxsignal from input_bitdepth; inf when sse == 0; 0 when not measured */
 } thor_hip_frame_stats;
 int thor_hip_frame_stats_count(const thor_hip_encoder* e, int stream);
 /* Record i (coding order) of a stream.  Returns 0, 1 on a bad argument. */
@@ -285,6 +292,16 @@ int thor_hip_kat_gather_bits(int n, const uint32_t* src, int src_words, const in
 /* Per-plane sums of squared differences between two planar 4:2:0 frames a and b (w x h; bitdepth 8: bytes, 9..12: uint16_t) through the
  * encoder's own kernel (k_frame_sse): out[0] Y, out[1] U, out[2] V, exact.  w, h: multiples of 8.  Returns 0, 1 = bad argument, 3 = no device. */
 int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth, unsigned long long out[3]);
+/* The three kernels behind input_bitdepth < bitdepth, each on one host frame (packed planar 4:2:0, w and h multiples of 8; input-depth samples are
+ * bytes for depth 8 and uint16_t otherwise, engine-depth samples uint16_t).  (bitdepth, input_bitdepth): (10, 8), (12, 8) or (12, 10).
+ * Returns 0, 1 = bad argument, 3 = no device.
+ * thor_hip_kat_depth_up: read_yuv_frame's widening (common/common_frame.c:491-499), out = in << (bitdepth - input_bitdepth).
+ * thor_hip_kat_depth_down: write_yuv_frame's rounding (:557-575), out = saturate((in + half) >> shift, input_bitdepth).
+ * thor_hip_frame_sse_depth: the sums of snr_yuv (common/snr.c:39-99) of two frames a and b at `bitdepth`: both rounded as above, then subtracted,
+ * squared and added, exact.  With bitdepth == input_bitdepth it is thor_hip_frame_sse. */
+int thor_hip_kat_depth_up(const void* in, int w, int h, int bitdepth, int input_bitdepth, uint16_t* out);
+int thor_hip_kat_depth_down(const uint16_t* in, int w, int h, int bitdepth, int input_bitdepth, void* out);
+int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int h, int bitdepth, int input_bitdepth, unsigned long long out[3]);
 
 /* Resources of the persistent superblock kernel (sample_bytes 1: 8-bit kernel, 2: 16-bit kernel, 0: the 8-bit kernel's second build for runs of few
  * streams - 256 registers, two workgroups per CU, chosen by the library when a run cannot fill more; THOR_HIP_KERNEL=std|lat|wide forces one; 3: its third build - eight wavefronts per workgroup, one workgroup per CU, for runs of very few streams) as the HIP runtime reports them: registers per lane,

@@ -6,7 +6,7 @@ fallback: importing works anywhere, but every call that computes requires the HI
 gfx950 device and fails loudly otherwise.
 """
 from .binding import (ThorParams, Encoder, lib, lib_path, load_config, sad_batch, interp_luma, code_tu_batch, deblock_frame,
-                      frame_sse, build_native, REPO_ROOT)
+                      frame_sse, frame_sse_depth, kat_depth_up, kat_depth_down, build_native, REPO_ROOT)
 
 __all__ = ['ThorParams', 'Encoder', 'lib', 'lib_path', 'load_config', 'sad_batch', 'interp_luma', 'code_tu_batch', 'deblock_frame',
-           'frame_sse', 'build_native', 'REPO_ROOT']
+           'frame_sse', 'frame_sse_depth', 'kat_depth_up', 'kat_depth_down', 'build_native', 'REPO_ROOT']

@@ -91,6 +91,8 @@ def lib():
         L.thor_hip_stream_data.restype = C.c_void_p
         L.thor_hip_stream_data.argtypes = [C.c_void_p, C.c_int]
         L.thor_hip_get_recon.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.thor_hip_frame_bytes.restype = C.c_size_t
+        L.thor_hip_frame_bytes.argtypes = [C.c_void_p]
         L.thor_hip_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_double)]
         L.thor_hip_kernel_time_reset.argtypes = [C.c_void_p]
         L.thor_hip_read_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
@@ -102,6 +104,9 @@ def lib():
         L.thor_hip_report.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
         L.thor_hip_stat_line.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
         L.thor_hip_frame_sse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
+        L.thor_hip_kat_depth_up.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_kat_depth_down.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_frame_sse_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -126,7 +131,8 @@ def load_config(cfg_path=None, **overrides):
 
 
 class Encoder:
-    """N independent closed streams encoded in lock step on one GPU (thor_hip_open ... thor_hip_close)."""
+    """N independent closed streams encoded in lock step on one GPU (thor_hip_open ... thor_hip_close).  Frames go in (stage) and come out
+    (recon) at the INPUT bit depth - `dtype` samples, `frame_bytes` bytes - also when params.bitdepth is higher (bitdepth=10, input_bitdepth=8)."""
 
     def __init__(self, params, num_streams=1, device=0):
         self.p = params
@@ -134,8 +140,9 @@ class Encoder:
         self.h = lib().thor_hip_open(C.byref(params), num_streams, device)
         if not self.h:
             raise RuntimeError('thor_hip_open failed (unsupported parameters?)')
-        self.sample_bytes = 2 if params.bitdepth > 8 else 1
-        self.frame_bytes = params.width * params.height * 3 // 2 * self.sample_bytes
+        self.dtype = _pix(params.input_bitdepth)
+        self.sample_bytes = self.dtype().itemsize
+        self.frame_bytes = lib().thor_hip_frame_bytes(self.h)
 
     def close(self):
         if self.h:
@@ -150,7 +157,8 @@ class Encoder:
             raise RuntimeError(f'thor_hip_stage_frame rc={rc}')
 
     def stage_device(self, stream, slot, dev_ptr):
-        """Stage a frame that already lives in HBM (device pointer to a contiguous planar 4:2:0 frame)."""
+        """Stage a frame that already lives in HBM (device pointer to a contiguous planar 4:2:0 frame of input-depth samples; 16-byte aligned
+        when input_bitdepth < bitdepth)."""
         rc = lib().thor_hip_stage_frame_device(self.h, stream, slot, C.c_void_p(dev_ptr))
         if rc:
             raise RuntimeError(f'thor_hip_stage_frame_device rc={rc}')
@@ -227,6 +235,7 @@ class Encoder:
         return C.string_at(lib().thor_hip_stream_data(self.h, stream), n)
 
     def recon(self, stream):
+        """Reconstruction of the stream's last coded frame: frame_bytes bytes (view them as self.dtype for the samples)."""
         out = np.empty(self.frame_bytes, dtype=np.uint8)
         rc = lib().thor_hip_get_recon(self.h, stream, out.ctypes.data_as(C.c_void_p))
         if rc:
@@ -516,4 +525,36 @@ def frame_sse(a, b, width, height, bitdepth=8):
     rc = lib().thor_hip_frame_sse(_vp(a), _vp(b), width, height, bitdepth, out)
     if rc:
         raise RuntimeError(f'thor_hip_frame_sse returned {rc}')
+    return [int(v) for v in out]
+
+
+def _depth_frame(a, depth, width, height):
+    a = np.ascontiguousarray(a, dtype=_pix(depth)).reshape(-1)
+    if a.size != width * height * 3 // 2:
+        raise ValueError('frame size does not match width x height 4:2:0')
+    return a
+
+
+def kat_depth_up(frame, width, height, bitdepth, input_bitdepth):
+    """thor_hip_kat_depth_up: a planar 4:2:0 frame of input-depth samples widened to `bitdepth` by the kernel that stages frames (uint16)."""
+    a = _depth_frame(frame, input_bitdepth, width, height)
+    out = np.zeros(a.size, dtype=np.uint16)
+    _kat('thor_hip_kat_depth_up', _vp(a), width, height, bitdepth, input_bitdepth, _vp(out))
+    return out
+
+
+def kat_depth_down(frame, width, height, bitdepth, input_bitdepth):
+    """thor_hip_kat_depth_down: a uint16 frame at `bitdepth` rounded and saturated to the input depth by the kernel behind Encoder.recon."""
+    a = _depth_frame(frame, 16, width, height)
+    out = np.zeros(a.size, dtype=_pix(input_bitdepth))
+    _kat('thor_hip_kat_depth_down', _vp(a), width, height, bitdepth, input_bitdepth, _vp(out))
+    return out
+
+
+def frame_sse_depth(a, b, width, height, bitdepth, input_bitdepth):
+    """thor_hip_frame_sse_depth: per-plane (Y, U, V) sums of squared differences of two frames at `bitdepth`, measured at the input depth."""
+    T = 16 if bitdepth > input_bitdepth else bitdepth
+    a = _depth_frame(a, T, width, height); b = _depth_frame(b, T, width, height)
+    out = (C.c_ulonglong * 3)()
+    _kat('thor_hip_frame_sse_depth', _vp(a), _vp(b), width, height, bitdepth, input_bitdepth, out)
     return [int(v) for v in out]

@@ -49,10 +49,11 @@ template <typename PIX> static void encode_frame_impl(struct thor_encoder_info* 
   thor_frame_info& fi = ei->frame_info;
   SeamState<PIX>*& st = seams<PIX>()[ei];
   if (!st) {
-    const SeqParams s = seam_params(*ei);
+    SeqParams s = seam_params(*ei);
     if (ep.subsample != 420 || (ep.log2_sb_size != 6 && ep.log2_sb_size != 7) || ep.qmtx || ep.max_delta_qp || ep.bitrate || ep.sync)
       seam_fatal("thor_hip: unsupported encoder parameters (need 4:2:0, 64x64 or 128x128 SB, no qmtx / delta-QP / rate control / sync)");
     if (unsupported(s)) seam_fatal("thor_hip: unsupported encoder parameters");
+    s.input_bitdepth = s.bitdepth;  // the caller's front end has widened `orig` and keeps `rec` at the internal depth: frames cross the seam as they are
     if (!ensure_init(getenv("THOR_HIP_DEVICE") ? atoi(getenv("THOR_HIP_DEVICE")) : 0)) seam_fatal("thor_hip: HIP device not usable");
     st = new SeamState<PIX>;
     st->eng.raw_frames = true;

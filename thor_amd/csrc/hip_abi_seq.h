@@ -50,8 +50,11 @@ static void from_seq(thor_hip_params* p, const SeqParams& src) {
 static int unsupported(const SeqParams& s) {
   // This path implements the high-efficiency low-delay operating point family; reject the rest
   // loudly rather than silently producing a different stream.
-  if (s.bitdepth != s.input_bitdepth || (s.bitdepth != 8 && s.bitdepth != 10 && s.bitdepth != 12))
-    return fprintf(stderr, "thor_hip: need bitdepth == input_bitdepth in {8, 10, 12}\n"), 1;
+  // input at a lower depth is widened on the way in (v << shift) and the reconstruction rounded back on the way out, as the reference does; the other
+  // direction is refused: the reference reads two-byte samples into one-byte frames there unless further options are given
+  auto depth_ok = [](int d) { return d == 8 || d == 10 || d == 12; };
+  if (!depth_ok(s.bitdepth) || !depth_ok(s.input_bitdepth) || s.input_bitdepth > s.bitdepth)
+    return fprintf(stderr, "thor_hip: need bitdepth and input_bitdepth in {8, 10, 12} with input_bitdepth <= bitdepth\n"), 1;
   if (s.num_reorder_pics != 0 && !s.dyadic_coding) return fprintf(stderr, "thor_hip: non-dyadic frame reordering is not implemented\n"), 1;
   if (s.num_reorder_pics < 0 || s.num_reorder_pics > 15 || (s.num_reorder_pics & (s.num_reorder_pics + 1)))
     return fprintf(stderr, "thor_hip: num_reorder_pics must be 0, 1, 3, 7 or 15\n"), 1;
@@ -120,6 +123,9 @@ thor_hip_encoder* thor_hip_open(const thor_hip_params* p, int num_streams, int d
   if (!p || num_streams < 1) return nullptr;
   SeqParams s = to_seq(*p);
   if (unsupported(s)) return nullptr;
+  // A parameter set that is in order still cannot be opened on a machine without a device: the constructor says so through its own failure channel
+  // (NULL and a message) and leaves the caller's process alive.  There is no CPU path; the entry points that compute keep ending the process.
+  if (thor_hip_device_count() < 1) return fprintf(stderr, "thor_hip: no HIP device available - this library has no CPU path\n"), nullptr;
   if (!ensure_init(device)) return nullptr;
   thor_hip_encoder* e = new thor_hip_encoder;
   e->sp = s;
@@ -169,7 +175,7 @@ int thor_hip_stage_frame(thor_hip_encoder* e, int stream, int slot, const void* 
     if (!v[slot].base_y) v[slot].alloc(e->sp.width, e->sp.height, 0);
     DevFrame<PIXT> keep = E.eng.st[stream].orig;
     E.eng.st[stream].orig = v[slot];
-    E.eng.upload_orig(stream, (const PIXT*)yuv);
+    E.eng.upload_orig(stream, yuv);
     E.eng.st[stream].orig = keep;
   });
   return 0;
@@ -177,13 +183,23 @@ int thor_hip_stage_frame(thor_hip_encoder* e, int stream, int slot, const void* 
 
 // Same as thor_hip_stage_frame for a frame that already lives in HBM (e.g. a torch CUDA tensor the caller derived from a
 // clip broadcast over RCCL): three device-to-device 2-D copies on the library's stream; the source may be released
-// when the call returns.
+// when the call returns.  With input_bitdepth < bitdepth the widen kernel reads the caller's buffer and writes the slot: no copy.
 int thor_hip_stage_frame_device(thor_hip_encoder* e, int stream, int slot, const void* dev_yuv) {
   if (!e || stream < 0 || stream >= e->S || slot < 0 || !dev_yuv) return 1;
   ENC_DISPATCH(e, {
     auto& v = E.staged[stream];
     if ((int)v.size() <= slot) v.resize(slot + 1);
     if (!v[slot].base_y) v[slot].alloc(e->sp.width, e->sp.height, 0);
+    if (E.eng.depth_shift() > 0) {
+      // the kernel reads vectors (tk_filters.h: depth_up_rows); frame sizes are multiples of 96 bytes, so the frames of an aligned clip all are
+      if ((uintptr_t)dev_yuv & 15) {
+        fprintf(stderr, "thor_hip: thor_hip_stage_frame_device needs a 16-byte aligned frame when input_bitdepth < bitdepth\n");
+        return 1;
+      }
+      E.eng.widen(dev_yuv, v[slot].p);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+      return 0;
+    }
     const PIXT* src = (const PIXT*)dev_yuv;
     const size_t B = sizeof(PIXT);
     for_yuv_planes(v[slot].p, e->sp.width, e->sp.height, [&](PIXT* d, int ds, size_t off, int pw, int ph) {
@@ -272,7 +288,7 @@ int thor_hip_encode_frame(thor_hip_encoder* e, const void* const* yuv) {
   ENC_DISPATCH(e, {
     std::vector<FrameParams> fp(e->S);
     for (int s = 0; s < e->S; s++) {
-      E.eng.upload_orig(s, (const PIXT*)yuv[s]);
+      E.eng.upload_orig(s, yuv[s]);
       if (!E.pending[s] && !E.eng.schedule(s)) { fprintf(stderr, "thor_hip: stream %d has no frame left to code\n", s); abort(); }
       E.pending[s] = 0;
       fp[s] = E.eng.st[s].cur;
@@ -290,9 +306,13 @@ const uint8_t* thor_hip_stream_data(const thor_hip_encoder* e, int stream) {
   if (!e || stream < 0 || stream >= e->S) return nullptr;
   return ENC_STREAM(e, stream, out.data());
 }
+size_t thor_hip_frame_bytes(const thor_hip_encoder* e) {
+  if (!e) return 0;
+  return (size_t)e->sp.width * e->sp.height * 3 / 2 * (e->sp.input_bitdepth > 8 ? 2 : 1);
+}
 int thor_hip_get_recon(thor_hip_encoder* e, int stream, void* yuv_out) {
   if (!e || stream < 0 || stream >= e->S || !yuv_out) return 1;
-  ENC_DISPATCH(e, { E.eng.download_rec(stream, (PIXT*)yuv_out); });
+  ENC_DISPATCH(e, { E.eng.download_rec(stream, yuv_out); });
   return 0;
 }
 void thor_hip_kernel_time(thor_hip_encoder*, double* sb_ms, long* sb_launches, double* filter_ms) {
@@ -333,18 +353,18 @@ int thor_hip_get_frame_stats(const thor_hip_encoder* e, int stream, int i, thor_
   for (int k = 0; k < 4; k++) { out->ref_array[k] = f.ref_array[k]; out->ref_frame_num[k] = f.ref_array[k] < 0 ? -1 : f.ref_frame_num[k]; }
   out->has_sse = f.has_sse;
   for (int k = 0; k < 3; k++) out->sse[k] = f.sse[k];
-  frame_psnr(f, e->sp.width, e->sp.height, e->sp.bitdepth, out->psnr);
+  frame_psnr(f, e->sp.width, e->sp.height, e->sp.input_bitdepth, out->psnr);
   return 0;
 }
 int thor_hip_report(const thor_hip_encoder* e, int stream, char* buf, size_t n) {
   const std::vector<FrameStat>* log = stream_log(e, stream);
   if (!log) return -1;
-  return copy_out(format_report(*log, stream_sh_bits(e, stream), e->sp.max_num_ref, e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.bitdepth), buf, n);
+  return copy_out(format_report(*log, stream_sh_bits(e, stream), e->sp.max_num_ref, e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.input_bitdepth), buf, n);
 }
 int thor_hip_stat_line(const thor_hip_encoder* e, int stream, int num_frames, char* buf, size_t n) {
   const std::vector<FrameStat>* log = stream_log(e, stream);
   if (!log) return -1;
-  return copy_out(format_stat_line(*log, stream_sh_bits(e, stream), e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.bitdepth, num_frames), buf, n);
+  return copy_out(format_stat_line(*log, stream_sh_bits(e, stream), e->sp.frame_rate, e->sp.width, e->sp.height, e->sp.input_bitdepth, num_frames), buf, n);
 }
 
 }  // extern "C"

@@ -326,6 +326,29 @@ template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const F
 template void launch_frame_sse<uint8_t>(const FrameJob<uint8_t>*, const FrameJob<uint8_t>*, int, unsigned long long*);
 template void launch_frame_sse<uint16_t>(const FrameJob<uint16_t>*, const FrameJob<uint16_t>*, int, unsigned long long*);
 
+// Input at a lower bit depth than the engine's: the three frame-level kernels on g_stream (tk_encoder.h declares them).  `packed`: a packed planar
+// 4:2:0 frame of input-depth samples in device memory, one byte per sample for depth 8 and two otherwise, 16-byte aligned.
+static dim3 depth_grid(int height) { return dim3((2 * height + 3) / 4); }   // Y, U and V rows, four wavefronts per workgroup
+void launch_depth_up(const void* packed, const Plane3<uint16_t>& dst, int width, int height, int bitdepth, int input_bitdepth) {
+  const int shift = bitdepth - input_bitdepth;
+  if (input_bitdepth == 8) hipLaunchKernelGGL(k_depth_up<uint8_t>, depth_grid(height), dim3(256), 0, g_stream, (const uint8_t*)packed, dst, width, height, shift);
+  else hipLaunchKernelGGL(k_depth_up<uint16_t>, depth_grid(height), dim3(256), 0, g_stream, (const uint16_t*)packed, dst, width, height, shift);
+  HIPCHECK(hipGetLastError());
+}
+void launch_depth_down(const Plane3<uint16_t>& src, void* packed, int width, int height, int bitdepth, int input_bitdepth) {
+  const int shift = bitdepth - input_bitdepth;
+  if (input_bitdepth == 8) hipLaunchKernelGGL(k_depth_down<uint8_t>, depth_grid(height), dim3(256), 0, g_stream, src, (uint8_t*)packed, width, height, shift, input_bitdepth);
+  else hipLaunchKernelGGL(k_depth_down<uint16_t>, depth_grid(height), dim3(256), 0, g_stream, src, (uint16_t*)packed, width, height, shift, input_bitdepth);
+  HIPCHECK(hipGetLastError());
+}
+void launch_frame_sse_depth(const FrameJob<uint16_t>* jobs, const FrameJob<uint16_t>* hjobs, int S, int bitdepth, int input_bitdepth, unsigned long long* out) {
+  if (S <= 0) return;
+  const int rows = 2 * hjobs[0].cfg.height;
+  const int blocks = (rows + 3) / 4 < 64 ? (rows + 3) / 4 : 64;
+  hipLaunchKernelGGL(k_frame_sse_depth, dim3(blocks, S), dim3(256), 0, g_stream, jobs, bitdepth - input_bitdepth, input_bitdepth, out);
+  HIPCHECK(hipGetLastError());
+}
+
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {
 // Owning device array of n elements, zeroed (dev_alloc clears), filled from `h` when given; freed with its scope.

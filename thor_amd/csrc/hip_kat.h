@@ -622,6 +622,56 @@ extern "C" int thor_hip_frame_sse(const void* a, const void* b, int w, int h, in
   KAT_BD(frame_sse_host<uint8_t>((const uint8_t*)a, (const uint8_t*)b, w, h, out),
          frame_sse_host<uint16_t>((const uint16_t*)a, (const uint16_t*)b, w, h, out));
 }
+// The three kernels of the mixed-depth path (bitdepth > input_bitdepth) on host frames: packed planar 4:2:0, input-depth samples one byte each for depth 8
+// and two otherwise, engine-depth samples uint16_t.
+static int kat_depth_args(const void* a, const void* b, int w, int h, int bitdepth, int input_bitdepth) {
+  auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };
+  return !a || !b || w % 8 || h % 8 || w < 8 || h < 8 || !ok(bitdepth) || !ok(input_bitdepth) || input_bitdepth >= bitdepth;
+}
+extern "C" int thor_hip_kat_depth_up(const void* in, int w, int h, int bitdepth, int input_bitdepth, uint16_t* out) {
+  if (kat_depth_args(in, out, w, h, bitdepth, input_bitdepth)) return 1;
+  if (!ensure_init_any()) return 3;
+  const size_t bytes = (size_t)w * h * 3 / 2 * (input_bitdepth > 8 ? 2 : 1);
+  DevBuf<uint8_t> packed(bytes, (const uint8_t*)in);
+  DevFrame<uint16_t> f;
+  f.alloc(w, h, 0);
+  launch_depth_up(packed, f.p, w, h, bitdepth, input_bitdepth);
+  backend::dev_sync();
+  download_yuv(f, out, w, h);
+  f.release();
+  return 0;
+}
+extern "C" int thor_hip_kat_depth_down(const uint16_t* in, int w, int h, int bitdepth, int input_bitdepth, void* out) {
+  if (kat_depth_args(in, out, w, h, bitdepth, input_bitdepth)) return 1;
+  if (!ensure_init_any()) return 3;
+  const size_t bytes = (size_t)w * h * 3 / 2 * (input_bitdepth > 8 ? 2 : 1);
+  DevBuf<uint8_t> packed(bytes);
+  DevFrame<uint16_t> f;
+  f.alloc(w, h, 0);
+  upload_yuv(f, in, w, h);
+  launch_depth_down(f.p, packed, w, h, bitdepth, input_bitdepth);
+  backend::d2h(out, packed, bytes);
+  f.release();
+  return 0;
+}
+extern "C" int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int h, int bitdepth, int input_bitdepth, unsigned long long out[3]) {
+  if (bitdepth == input_bitdepth) return thor_hip_frame_sse(a, b, w, h, bitdepth, out);
+  if (!out || kat_depth_args(a, b, w, h, bitdepth, input_bitdepth)) return 1;
+  if (!ensure_init_any()) return 3;
+  DevFrame<uint16_t> fa, fb;
+  fa.alloc(w, h, 0); fb.alloc(w, h, 0);
+  upload_yuv(fa, (const uint16_t*)a, w, h); upload_yuv(fb, (const uint16_t*)b, w, h);
+  FrameJob<uint16_t> J;
+  memset(&J, 0, sizeof(J));
+  J.cfg.width = w; J.cfg.height = h; J.orig = fa.p; J.rec = fb.p;
+  DevBuf<FrameJob<uint16_t>> dj(1, &J);
+  DevBuf<unsigned long long> dout(4);  // zeroed
+  launch_frame_sse_depth(dj, &J, 1, bitdepth, input_bitdepth, dout);
+  backend::dev_sync();
+  backend::d2h(out, dout, 3 * sizeof(unsigned long long));
+  fa.release(); fb.release();
+  return 0;
+}
 extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
   KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),
          kat_interpolate<uint16_t>((const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, (uint16_t*)out_yuv));

@@ -1,5 +1,6 @@
 // hip_kernels.h - the frame-level kernels of the throughput build (part of the translation unit thor_hip.cpp, device-only): deblocking, padded
-// reference, frame SSE, bit gather, CDEF, CLPF, the temporally interpolated reference.  Launched by hip_backend.h.
+// reference, frame SSE, bit gather, CDEF, CLPF, the temporally interpolated reference, the bit-depth conversion of frames that enter and leave at a lower
+// input depth.  Launched by hip_backend.h.
 // The dependency-driven persistent superblock kernel is not here: a task is (stream, superblock), SB(k,l) needs its left neighbour (k,l-1) and its
 // up-right neighbour (k-1,l+1) ((k-1,l) in the last column) - SURVEY.md Appendix A; the kernel is in tk_kernel.h, its ready-task queue in tk_sched.h.
 #pragma once
@@ -181,5 +182,27 @@ template <typename PIX> __global__ __launch_bounds__(64) void k_interp_mc(const 
 template <typename PIX> __global__ void k_interp_pad(const idev::Job<PIX>* jobs) {
   const idev::Job<PIX>& J = jobs[blockIdx.y];
   idev::pad_item(J, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+}
+
+// ---- input at a lower bit depth than the engine's (tk_filters.h: depth_up_rows, depth_down_rows, frame_sse_depth_rows) --------
+// One frame per launch, one wavefront per row (blockIdx.x * 4 + wave, + 4 * gridDim.x, ...), lanes along the row.
+template <typename SRC> __global__ __launch_bounds__(256) void k_depth_up(const SRC* src, Plane3<uint16_t> dst, int width, int height, int shift) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  depth_up_rows(src, dst, width, height, shift, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64);
+}
+template <typename DST> __global__ __launch_bounds__(256) void k_depth_down(Plane3<uint16_t> src, DST* dst, int width, int height, int shift, int input_bitdepth) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  depth_down_rows(src, dst, width, height, shift, input_bitdepth, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64);
+}
+// k_frame_sse at the input depth: same grid, same reduction, same slots.
+__global__ __launch_bounds__(256) void k_frame_sse_depth(const FrameJob<uint16_t>* jobs, int shift, int input_bitdepth, unsigned long long* out) {
+  const FrameJob<uint16_t>& J = jobs[blockIdx.y];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  unsigned long long acc[3] = {0, 0, 0};
+  frame_sse_depth_rows(J.orig, J.rec, J.cfg.width, J.cfg.height, shift, input_bitdepth, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64, acc);
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long v = wave_sum64_dpp(acc[k]);
+    if (lane == 0 && v) atomicAdd(&out[4 * (size_t)blockIdx.y + k], v);
+  }
 }
 }  // namespace tk

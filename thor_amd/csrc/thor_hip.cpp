@@ -1,8 +1,8 @@
 // thor_hip.cpp - libthor_hip.so: gfx950 kernels, device backend and the C ABI (include/thor_hip.h).
 // One workgroup of 4 wavefronts encodes one 128x128 superblock at a time (wave 0 walks the quadtree, all four share the
 // trials of each block decision); one persistent, dependency-driven launch per frame covers every superblock of every stream (SB(k,l) needs (k,l-1) and
-// (k-1,l+1)).  There is NO CPU path in this library: every entry point aborts if no
-// HIP device is usable.
+// (k-1,l+1)).  There is NO CPU path in this library: every entry point that computes aborts if no
+// HIP device is usable (thor_hip_open reports it by returning NULL).
 // This file is the ONE translation unit of the throughput build (a kernel can only be launched from the unit that defines it: the library is built
 // without relocatable device code).  Its parts, by role, are the hip_*.h headers included at the end - device-only, never part of the host simulation:
 //   hip_kernels.h   the frame-level __global__ kernels (the superblock kernel itself is tk_kernel.h)

@@ -150,20 +150,20 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   const SeqParams& p = a.sp;
   FILE* fi = fopen(a.infile.c_str(), "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", a.infile.c_str()); return 2; }
-  const size_t fsz = (size_t)p.width * p.height * 3 / 2;
   Engine<PIX> eng;
   eng.frame_distortion = a.snrcalc != 0;
   eng.open(p, a.streams);
-  std::vector<PIX> frame(fsz), rec(fsz);
+  const size_t fsz = eng.frame_bytes();  // the files hold input-depth samples (-if and -rf: common/common_frame.c:484-650)
+  std::vector<uint8_t> frame(fsz), rec(fsz);
   std::vector<FILE*> fr(a.streams, nullptr);
   auto name = [&](const std::string& base, int s) { return a.streams == 1 ? base : base + "." + std::to_string(s); };
   for (int s = 0; s < a.streams; s++)
     if (!a.recfile.empty()) fr[s] = fopen(name(a.recfile, s).c_str(), "wb");
   // all streams run in lock step through their (identical) coding-order schedules
   fseek(fi, 0, SEEK_END);
-  const int file_frames = (int)(ftell(fi) / (long)(fsz * sizeof(PIX)));
+  const int file_frames = (int)(ftell(fi) / (long)fsz);
   for (int s = 0; s < a.streams; s++) eng.begin_sequence(s, a.skip + s * a.num_frames, a.num_frames, file_frames);
-  std::vector<std::vector<PIX>> recs((size_t)a.streams * a.num_frames);  // recon in display order
+  std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
   // THOR_STAGGER=1 (tests): the streams in two groups half a frame apart (Engine::encode_run) instead of lock step
   if (getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER")) && a.streams > 1) {
     int rc = 0;
@@ -171,7 +171,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
         [&](int s) -> bool {
           if (!eng.schedule(s)) return false;
           const size_t idx = (size_t)eng.st[s].cur_abs;
-          if (fseek(fi, (long)(idx * fsz * sizeof(PIX)), SEEK_SET) || fread(frame.data(), sizeof(PIX), fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); rc = 3; return false; }
+          if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); rc = 3; return false; }
           eng.upload_orig(s, frame.data());
           return true;
         },
@@ -188,7 +188,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       if (!eng.schedule(s)) continue;
       active++;
       size_t idx = (size_t)eng.st[s].cur_abs;
-      if (fseek(fi, (long)(idx * fsz * sizeof(PIX)), SEEK_SET) || fread(frame.data(), sizeof(PIX), fsz, fi) != fsz) {
+      if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) {
         fprintf(stderr, "short read at frame %zu\n", idx);
         return 3;
       }
@@ -221,8 +221,8 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   for (int s = 0; s < a.streams; s++)
     if (fr[s])
       for (int n = 0; n < a.num_frames; n++) {
-        const std::vector<PIX>& r = recs[(size_t)s * a.num_frames + n];
-        if (!r.empty()) fwrite(r.data(), sizeof(PIX), fsz, fr[s]);
+        const std::vector<uint8_t>& r = recs[(size_t)s * a.num_frames + n];
+        if (!r.empty()) fwrite(r.data(), 1, fsz, fr[s]);
       }
   for (int s = 0; s < a.streams; s++) {
     if (fr[s]) fclose(fr[s]);
@@ -234,9 +234,9 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   }
   for (int s = 0; s < a.streams; s++) {
     if (a.streams > 1) printf("stream %d\n", s);
-    fputs(format_report(eng.st[s].log, eng.st[s].sh_bits, p.max_num_ref, p.frame_rate, p.width, p.height, p.bitdepth).c_str(), stdout);
+    fputs(format_report(eng.st[s].log, eng.st[s].sh_bits, p.max_num_ref, p.frame_rate, p.width, p.height, p.input_bitdepth).c_str(), stdout);
     if (!a.statfile.empty())
-      append_stat_file(a.statfile.c_str(), format_stat_line(eng.st[s].log, eng.st[s].sh_bits, p.frame_rate, p.width, p.height, p.bitdepth, a.num_frames));
+      append_stat_file(a.statfile.c_str(), format_stat_line(eng.st[s].log, eng.st[s].sh_bits, p.frame_rate, p.width, p.height, p.input_bitdepth, a.num_frames));
   }
   fflush(stdout);
   eng.close();

@@ -63,6 +63,12 @@ template <typename PIX> void run_interp(const idev::Job<PIX>* jobs, const idev::
 // Per-plane sums of squared differences orig - rec of S streams into out[4 * s + plane] (added: the caller clears the slots), one launch
 // (hip_kernels.h: k_frame_sse, launched by hip_backend.h).  The host build calls frame_sse_rows directly (Engine::finish_frames).
 template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const FrameJob<PIX>* hjobs, int S, unsigned long long* out);
+// Input at a lower bit depth than the engine's (bitdepth > input_bitdepth; tk_filters.h: depth_up_rows, depth_down_rows, frame_sse_depth_rows), one
+// launch each on the library's stream.  `packed`: a packed planar 4:2:0 frame of input-depth samples in device memory.  The host build calls the row
+// functions directly (Engine::widen / narrow / finish_frames).
+void launch_depth_up(const void* packed, const Plane3<uint16_t>& dst, int width, int height, int bitdepth, int input_bitdepth);
+void launch_depth_down(const Plane3<uint16_t>& src, void* packed, int width, int height, int bitdepth, int input_bitdepth);
+void launch_frame_sse_depth(const FrameJob<uint16_t>* jobs, const FrameJob<uint16_t>* hjobs, int S, int bitdepth, int input_bitdepth, unsigned long long* out);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -407,6 +413,11 @@ template <typename PIX> class Engine {
   std::vector<idev::Job<PIX>> h_ijobs;
   bool frame_distortion = false;        // measure the per-plane SSE of every coded frame (off: a frame's launches and copies are unchanged)
   unsigned long long* d_sse = nullptr;  // [S][4]: Y, U, V sums of the frame just finished (allocated on first use)
+  void* d_packed = nullptr;             // input_bitdepth < bitdepth: one packed frame of input-depth samples, staging for upload_orig / download_rec
+
+  // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
+  int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
+  size_t frame_bytes() const { return (size_t)sp.width * sp.height * 3 / 2 * (sp.input_bitdepth > 8 ? 2 : 1); }
 
   void open(const SeqParams& p, int num_streams) {
     sp = p; S = num_streams;
@@ -487,6 +498,7 @@ template <typename PIX> class Engine {
     d_stats = (unsigned long long*)backend::dev_alloc(8 * sizeof(unsigned long long));
     backend::dev_memset(d_stats, 0, 8 * sizeof(unsigned long long));
     if (p.interp_ref && !external_interp) { d_ijobs = (idev::Job<PIX>*)backend::dev_alloc(sizeof(idev::Job<PIX>) * S); h_ijobs.resize(S); }
+    if (depth_shift() > 0) d_packed = backend::dev_alloc(frame_bytes());
   }
   size_t clpf_stat_words() const { return 4 * ((size_t)(sp.width / 8) * (sp.height / 8) + 2 * (size_t)(sp.width / 16) * (sp.height / 16)); }
   void close() {
@@ -513,10 +525,40 @@ template <typename PIX> class Engine {
     backend::dev_free(d_stats); d_stats = nullptr;
     backend::dev_free(d_ijobs); d_ijobs = nullptr;
     backend::dev_free(d_sse); d_sse = nullptr;
+    backend::dev_free(d_packed); d_packed = nullptr;
   }
 
-  // planar 4:2:0 frame in host memory -> device `orig` of stream s
-  void upload_orig(int s, const PIX* yuv) {
+  // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
+  // input_bitdepth < bitdepth, which implies 16-bit planes.  Asynchronous on the device: ordered with the engine's other work.
+  void widen(const void* packed, const Plane3<PIX>& dst) {
+    if constexpr (sizeof(PIX) == 2) {
+#if TK_HOST
+      if (sp.input_bitdepth == 8) depth_up_rows((const uint8_t*)packed, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+      else depth_up_rows((const uint16_t*)packed, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+#else
+      launch_depth_up(packed, dst, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+    }
+  }
+  void narrow(const Plane3<PIX>& src, void* packed) {
+    if constexpr (sizeof(PIX) == 2) {
+#if TK_HOST
+      if (sp.input_bitdepth == 8) depth_down_rows(src, (uint8_t*)packed, sp.width, sp.height, depth_shift(), sp.input_bitdepth, 0, 1, 0, 1);
+      else depth_down_rows(src, (uint16_t*)packed, sp.width, sp.height, depth_shift(), sp.input_bitdepth, 0, 1, 0, 1);
+#else
+      launch_depth_down(src, packed, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+    }
+  }
+
+  // planar 4:2:0 frame of input-depth samples in host memory -> device `orig` of stream s
+  void upload_orig(int s, const void* yuv_in) {
+    if (depth_shift() > 0) {  // the narrow frame travels; the device widens it
+      backend::h2d(d_packed, yuv_in, frame_bytes());
+      widen(d_packed, st[s].orig.p);
+      return;
+    }
+    const PIX* yuv = (const PIX*)yuv_in;
     const int w = sp.width, h = sp.height;
     std::vector<PIX> tmp;
     DevFrame<PIX>& f = st[s].orig;
@@ -545,7 +587,14 @@ template <typename PIX> class Engine {
     for (int i = 0; i < h / 2; i++) memcpy(&tmp[(size_t)i * f.p.sc], v + (size_t)i * sc, (w / 2) * sizeof(PIX));
     backend::h2d(f.p.v, tmp.data(), tmp.size() * sizeof(PIX));
   }
-  void download_rec(int s, PIX* yuv) {
+  // reconstruction of stream s -> planar 4:2:0 frame of input-depth samples in host memory (what the reference writes with -rf)
+  void download_rec(int s, void* yuv_out) {
+    if (depth_shift() > 0) {
+      narrow(st[s].rec.p, d_packed);
+      backend::d2h(yuv_out, d_packed, frame_bytes());
+      return;
+    }
+    PIX* yuv = (PIX*)yuv_out;
     const int w = sp.width, h = sp.height;
     DevFrame<PIX>& f = st[s].rec;
     std::vector<PIX> tmp((size_t)f.p.sy * h);
@@ -797,11 +846,25 @@ template <typename PIX> class Engine {
     if (frame_distortion) {  // per-plane SSE of the final reconstructions (after deblocking, CDEF, CLPF)
       if (!d_sse) d_sse = (unsigned long long*)backend::dev_alloc((size_t)S * 4 * sizeof(unsigned long long));
       backend::dev_memset(d_sse + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long));
+      bool at_input_depth = false;  // input_bitdepth < bitdepth: the sums snr_yuv forms, both frames rounded back to the input depth
+      if constexpr (sizeof(PIX) == 2) {
+        if (depth_shift() > 0) {
+          at_input_depth = true;
 #if TK_HOST
-      for (int s = first; s < end; s++) frame_sse_rows(h_jobs[s].orig, h_jobs[s].rec, sp.width, sp.height, 0, 1, 0, 1, d_sse + (size_t)s * 4);
+          for (int s = first; s < end; s++)
+            frame_sse_depth_rows(h_jobs[s].orig, h_jobs[s].rec, sp.width, sp.height, depth_shift(), sp.input_bitdepth, 0, 1, 0, 1, d_sse + (size_t)s * 4);
 #else
-      launch_frame_sse<PIX>(d_jobs + first, h_jobs.data() + first, count, d_sse + (size_t)first * 4);
+          launch_frame_sse_depth(d_jobs + first, h_jobs.data() + first, count, sp.bitdepth, sp.input_bitdepth, d_sse + (size_t)first * 4);
 #endif
+        }
+      }
+      if (!at_input_depth) {
+#if TK_HOST
+        for (int s = first; s < end; s++) frame_sse_rows(h_jobs[s].orig, h_jobs[s].rec, sp.width, sp.height, 0, 1, 0, 1, d_sse + (size_t)s * 4);
+#else
+        launch_frame_sse<PIX>(d_jobs + first, h_jobs.data() + first, count, d_sse + (size_t)first * 4);
+#endif
+      }
     }
     backend::dev_sync();
     if (frame_distortion) {

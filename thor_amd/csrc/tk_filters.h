@@ -166,4 +166,107 @@ TK_DEV void frame_sse_rows(const Plane3<PIX>& org, const Plane3<PIX>& rec, int w
   }
 }
 
+// ---- input at a lower bit depth than the engine's (shift = bitdepth - input_bitdepth > 0) --------------------------------
+// The frame enters widened and leaves rounded back, as the reference reads and writes it (common/common_frame.c:484-545, :549-650), and its
+// distortion is measured at the input depth (common/snr.c:39-61).  A packed frame is Y, U, V one after the other without row padding; its
+// rows are only as aligned as the geometry guarantees (widths are multiples of 8 samples, chroma widths of 4), so a packed luma row moves in
+// vectors of 8 samples and a chroma row in vectors of 4.  The frame itself must start on a 16-byte boundary.  One work item per row (Y rows,
+// then U, then V) like make_ref_rows; `lane`/`nlanes` stride along the row in those vectors.
+template <typename T, int N> struct alignas(N * sizeof(T)) DepthVec { T v[N]; };
+
+// write_yuv_frame / snr_yuv: saturate((v + round) >> shift, input_bitdepth).  Live: 1023 at 10 bits rounds to 256 at 8.
+TK_DEV int depth_round(int v, int shift, int maxv) {
+  const int r = (v + (1 << (shift - 1))) >> shift;
+  return r > maxv ? maxv : r;
+}
+
+// Row `it` of a 4:2:0 frame of `planes` against the packed frame `packed`: the plane row, the packed row, the width in samples.
+template <typename PIX, typename PK>
+TK_DEV void depth_row(const Plane3<PIX>& planes, PK* packed, int width, int height, int it, PIX*& prow, PK*& krow, int& w) {
+  const size_t ny = (size_t)width * height, nc = (size_t)(width / 2) * (height / 2);
+  if (it < height) { prow = planes.y + (size_t)it * planes.sy; krow = packed + (size_t)it * width; w = width; }
+  else if (it < height + height / 2) { const int r = it - height; prow = planes.u + (size_t)r * planes.sc; krow = packed + ny + (size_t)r * (width / 2); w = width / 2; }
+  else { const int r = it - height - height / 2; prow = planes.v + (size_t)r * planes.sc; krow = packed + ny + nc + (size_t)r * (width / 2); w = width / 2; }
+}
+
+// read_yuv_frame: packed input-depth samples (SRC = uint8_t for depth 8, uint16_t otherwise) -> the engine's planes, v << shift.
+template <typename SRC>
+TK_DEV void depth_up_rows(const SRC* src, const Plane3<uint16_t>& dst, int width, int height, int shift, int gid, int gsize, int lane, int nlanes) {
+  const int total = height + height;  // Y rows + U rows + V rows
+  for (int it = gid; it < total; it += gsize) {
+    uint16_t* d;
+    const SRC* s;
+    int w;
+    depth_row(dst, src, width, height, it, d, s, w);
+    if (it < height)
+      for (int i = lane; i < w / 8; i += nlanes) {
+        const DepthVec<SRC, 8> a = ((const DepthVec<SRC, 8>*)s)[i];
+        DepthVec<uint16_t, 8> o;
+        for (int k = 0; k < 8; k++) o.v[k] = (uint16_t)((int)a.v[k] << shift);
+        ((DepthVec<uint16_t, 8>*)d)[i] = o;
+      }
+    else
+      for (int i = lane; i < w / 4; i += nlanes) {
+        const DepthVec<SRC, 4> a = ((const DepthVec<SRC, 4>*)s)[i];
+        DepthVec<uint16_t, 4> o;
+        for (int k = 0; k < 4; k++) o.v[k] = (uint16_t)((int)a.v[k] << shift);
+        ((DepthVec<uint16_t, 4>*)d)[i] = o;
+      }
+  }
+}
+
+// write_yuv_frame: the engine's planes -> packed input-depth samples (DST = uint8_t for depth 8, uint16_t otherwise), rounded and saturated.
+template <typename DST>
+TK_DEV void depth_down_rows(const Plane3<uint16_t>& src, DST* dst, int width, int height, int shift, int input_bitdepth, int gid, int gsize, int lane,
+                            int nlanes) {
+  const int maxv = (1 << input_bitdepth) - 1;
+  const int total = height + height;
+  for (int it = gid; it < total; it += gsize) {
+    uint16_t* s;
+    DST* d;
+    int w;
+    depth_row(src, dst, width, height, it, s, d, w);
+    if (it < height)
+      for (int i = lane; i < w / 8; i += nlanes) {
+        const DepthVec<uint16_t, 8> a = ((const DepthVec<uint16_t, 8>*)s)[i];
+        DepthVec<DST, 8> o;
+        for (int k = 0; k < 8; k++) o.v[k] = (DST)depth_round(a.v[k], shift, maxv);
+        ((DepthVec<DST, 8>*)d)[i] = o;
+      }
+    else
+      for (int i = lane; i < w / 4; i += nlanes) {
+        const DepthVec<uint16_t, 4> a = ((const DepthVec<uint16_t, 4>*)s)[i];
+        DepthVec<DST, 4> o;
+        for (int k = 0; k < 4; k++) o.v[k] = (DST)depth_round(a.v[k], shift, maxv);
+        ((DepthVec<DST, 4>*)d)[i] = o;
+      }
+  }
+}
+
+// frame_sse_rows at the input depth, the sum snr_yuv forms: both frames go through the round-and-saturate step before they are subtracted.
+// Same work split and exact 64-bit sums; every row, luma too, is read in vectors of 4 samples (8 bytes), which divide every row width, so there is
+// no tail loop (a frame's worth of this is ~20 us at 1920x1080: the wider luma vectors of frame_sse_rows would buy nothing).
+TK_DEV void frame_sse_depth_rows(const Plane3<uint16_t>& org, const Plane3<uint16_t>& rec, int width, int height, int shift, int input_bitdepth, int gid,
+                                 int gsize, int lane, int nlanes, unsigned long long acc[3]) {
+  const int maxv = (1 << input_bitdepth) - 1;
+  const int total = height + height;
+  for (int it = gid; it < total; it += gsize) {
+    const int pl = it < height ? 0 : it < height + height / 2 ? 1 : 2;
+    const int r = pl == 0 ? it : pl == 1 ? it - height : it - height - height / 2;
+    const int w = pl == 0 ? width : width / 2;
+    const uint16_t* a = pl == 0 ? org.y + (size_t)r * org.sy : (pl == 1 ? org.u : org.v) + (size_t)r * org.sc;
+    const uint16_t* b = pl == 0 ? rec.y + (size_t)r * rec.sy : (pl == 1 ? rec.u : rec.v) + (size_t)r * rec.sc;
+    unsigned long long s = 0;
+    for (int i = lane; i < w / 4; i += nlanes) {   // 4 samples = 8 bytes: divides every row
+      const DepthVec<uint16_t, 4> va = ((const DepthVec<uint16_t, 4>*)a)[i], vb = ((const DepthVec<uint16_t, 4>*)b)[i];
+      unsigned int q = 0;  // 4 squares of at most 1023^2
+      for (int k = 0; k < 4; k++) { const int d = depth_round(va.v[k], shift, maxv) - depth_round(vb.v[k], shift, maxv); q += (unsigned int)(d * d); }
+      s += q;
+    }
+    acc[0] += pl == 0 ? s : 0;  // constant indices: acc stays in registers on the device
+    acc[1] += pl == 1 ? s : 0;
+    acc[2] += pl == 2 ? s : 0;
+  }
+}
+
 }  // namespace tk

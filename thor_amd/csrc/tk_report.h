@@ -25,7 +25,8 @@ struct FrameStat {
 
 // snr_yuv (common/snr.c:56-62): plse = sse / (maxsignal * maxsignal * ydim * xdim) in double, in that order; the Y loop's float cast
 // of each square is exact (4095^2 < 2^24) and so is the double sum of integers below 2^53: the exact sum gives the same double.
-// sse == 0 gives inf, as the reference prints it.
+// sse == 0 gives inf, as the reference prints it.  `bitdepth`, here and below, is the INPUT bit depth: snr_yuv takes maxsignal from it and, when the
+// encoder works at a higher depth, rounds both frames back to it before it subtracts them (common/snr.c:39-61; the engine's sums are formed that way).
 inline double psnr_of(unsigned long long sse, int bitdepth, unsigned int xdim, unsigned int ydim) {
   const double maxsignal = (double)((1 << bitdepth) - 1);
   const double plse = (double)sse / (maxsignal * maxsignal * ydim * xdim);

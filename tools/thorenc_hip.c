@@ -60,10 +60,11 @@ int main(int argc, char** argv) {
   if (!inf) { fprintf(stderr, "usage: %s -cf cfg -if in.yuv -width W -height H -qp Q -n N ...\n", argv[0]); return 2; }
   FILE* fi = fopen(inf, "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", inf); return 2; }
-  size_t fsz = (size_t)p.width * p.height * 3 / 2 * (p.bitdepth > 8 ? 2 : 1);
-  unsigned char* frame = (unsigned char*)malloc(fsz);
+  if (p.input_bitdepth > p.bitdepth) { fprintf(stderr, "Run-time error...\ninput_bitdepth %d above bitdepth %d is not implemented by this path\n...now exiting to system...\n", p.input_bitdepth, p.bitdepth); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
+  size_t fsz = thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth */
+  unsigned char* frame = (unsigned char*)malloc(fsz);
   thor_hip_set_frame_distortion(e, snrcalc != 0);
   for (int s = 0; s < S; s++)
     for (int f = 0; f < n; f++) {
