@@ -138,6 +138,42 @@ const uint8_t* thor_hip_stream_data(const thor_hip_encoder* e, int stream);
  * display order), thor_hip_frame_bytes(e) bytes of input-depth samples. */
 int thor_hip_get_recon(thor_hip_encoder* e, int stream, void* yuv_out);
 
+/* Frames in the layouts decoders, capture cards and GPU pipelines hold: semi-planar chroma (NV12 / NV21 at 8 bits; P010 / P012 / P016
+ * above), a row pitch wider than the picture, 16-bit samples in the high bits.  A layout is given per call, not in thor_hip_params.
+ * All fields 0 apart from `size` is the packed planar frame of the calls above.  Samples are input_bitdepth wide: one byte for 8 bits,
+ * two bytes (little-endian) otherwise.  One kernel converts between the layout and the encoder's planes, depth conversion included:
+ *   staging:  x = msb_aligned ? s >> (16 - input_bitdepth) : s;  the staged sample is x << (bitdepth - input_bitdepth)
+ *   fetching: r = the reconstruction rounded and saturated to input_bitdepth (thor_hip_get_recon's value);
+ *             written is msb_aligned ? r << (16 - input_bitdepth) : r
+ * Bytes of a row beyond the picture's width and bytes between the planes are never read on staging and never written on fetching.
+ * Planes must not overlap (not checked). */
+enum { THOR_HIP_CHROMA_PLANAR = 0, THOR_HIP_CHROMA_UV = 1, THOR_HIP_CHROMA_VU = 2 };
+typedef struct thor_hip_frame_layout {
+  int    size;         /* sizeof(thor_hip_frame_layout): lets the struct grow later */
+  int    chroma;       /* planar U,V planes | one interleaved plane U0 V0 U1 V1.. | V0 U0.. */
+  int    msb_aligned;  /* 0: value in the low bits.  1: value << (16 - input_bitdepth), the P010 / P012 / P016
+                          convention; only legal with input_bitdepth > 8 */
+  int    pitch_y;      /* bytes between luma rows; 0 = tight */
+  int    pitch_c;      /* bytes between rows of each chroma plane (or of the interleaved plane); 0 = tight */
+  size_t offset_u;     /* bytes from the base to the U plane (or the interleaved plane);
+                          0 = directly after luma (pitch_y * height) */
+  size_t offset_v;     /* planar only: bytes from the base to the V plane; 0 = directly after U (pitch_c * height / 2) */
+} thor_hip_frame_layout;
+/* Bytes a frame in `layout` spans from its base, whole pitch of the last row included (width * height * 3 / 2 samples when tight);
+ * 0 if the layout is refused: `size` is wrong, `chroma` is unknown, a pitch is below the row's bytes, a pitch or an offset is no
+ * multiple of the sample size, msb_aligned is set with 8-bit input.  thor_hip_layout_bytes_for needs no encoder (and no device). */
+size_t thor_hip_layout_bytes(const thor_hip_encoder* e, const thor_hip_frame_layout* layout);
+size_t thor_hip_layout_bytes_for(int width, int height, int input_bitdepth, const thor_hip_frame_layout* layout);
+/* thor_hip_stage_frame / thor_hip_stage_frame_device (on_device != 0: `frame` is a device pointer) for a frame in `layout`.  A device
+ * frame is read by the kernel that writes the slot: no intermediate copy, no alignment demanded beyond the sample size (16-byte aligned
+ * base and pitches move in 16-byte vectors, anything else sample by sample).  A host frame's thor_hip_layout_bytes bytes are copied
+ * once into a device buffer the encoder keeps and the same kernel runs.  Synchronous at return, on the library's stream, like
+ * thor_hip_stage_frame_device.  Returns 0; 1 for a bad argument, a refused layout or a base pointer that is not sample-aligned -
+ * found before the device is touched. */
+int thor_hip_stage_frame_layout(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_frame_layout* layout, int on_device);
+/* thor_hip_get_recon into a frame in `layout`, in host memory or (on_device != 0) in device memory.  Same return values. */
+int thor_hip_get_recon_layout(thor_hip_encoder* e, int stream, void* frame, const thor_hip_frame_layout* layout, int on_device);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -302,6 +338,15 @@ int thor_hip_frame_sse(const void* a, const void* b, int w, int h, int bitdepth,
 int thor_hip_kat_depth_up(const void* in, int w, int h, int bitdepth, int input_bitdepth, uint16_t* out);
 int thor_hip_kat_depth_down(const uint16_t* in, int w, int h, int bitdepth, int input_bitdepth, void* out);
 int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int h, int bitdepth, int input_bitdepth, unsigned long long out[3]);
+/* The two kernels behind thor_hip_stage_frame_layout / thor_hip_get_recon_layout (k_layout_in, k_layout_out) on host buffers, without an encoder.
+ * `planar_*`: a packed planar 4:2:0 frame at `bitdepth` (bytes for 8, uint16_t otherwise); `src` / `dst`: thor_hip_layout_bytes_for(w, h,
+ * input_bitdepth, layout) bytes in `layout`.  Depths: 8, 10 or 12 with input_bitdepth <= bitdepth.  The device copy of the layout buffer keeps the
+ * host pointer's offset from a 16-byte boundary, so a base that is off such a boundary takes the kernel's sample-by-sample path.
+ * thor_hip_kat_layout_out's `dst` holds 64 guard bytes after the layout; all of it is uploaded before the kernel runs and downloaded afterwards, so a byte
+ * the kernel must not write (row padding, gaps between planes, the guard) comes back as it was.
+ * Returns 0, 1 = bad argument or refused layout (before the device is touched), 3 = no device. */
+int thor_hip_kat_layout_in(const void* src, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* planar_out);
+int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* dst);
 
 /* Resources of the persistent superblock kernel (sample_bytes 1: 8-bit kernel, 2: 16-bit kernel, 0: the 8-bit kernel's second build for runs of few
  * streams - 256 registers, two workgroups per CU, chosen by the library when a run cannot fill more; THOR_HIP_KERNEL=std|lat|wide forces one; 3: its third build - eight wavefronts per workgroup, one workgroup per CU, for runs of very few streams) as the HIP runtime reports them: registers per lane,

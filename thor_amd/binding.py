@@ -67,6 +67,39 @@ class FrameStats(C.Structure):
                 ('psnr', C.c_double * 3)]
 
 
+CHROMA_PLANAR, CHROMA_UV, CHROMA_VU = 0, 1, 2   # THOR_HIP_CHROMA_*
+
+
+class FrameLayout(C.Structure):
+    """thor_hip_frame_layout (include/thor_hip.h): where the samples of a 4:2:0 frame lie in a buffer.  Pitches and offsets in bytes, 0 = tight /
+    adjacent.  Samples are input_bitdepth wide (one byte for 8 bits, two otherwise); msb_aligned: they sit in the high bits of 16-bit words."""
+    _fields_ = [('size', C.c_int), ('chroma', C.c_int), ('msb_aligned', C.c_int), ('pitch_y', C.c_int), ('pitch_c', C.c_int),
+                ('offset_u', C.c_size_t), ('offset_v', C.c_size_t)]
+
+    def __init__(self, chroma=CHROMA_PLANAR, msb_aligned=0, pitch_y=0, pitch_c=0, offset_u=0, offset_v=0):
+        super().__init__(C.sizeof(FrameLayout), chroma, msb_aligned, pitch_y, pitch_c, offset_u, offset_v)
+
+    @classmethod
+    def planar(cls, pitch_y=0, pitch_c=0, offset_u=0, offset_v=0, msb_aligned=0):
+        """Y, U and V planes (I420; YV12 by giving offset_v below offset_u)."""
+        return cls(CHROMA_PLANAR, msb_aligned, pitch_y, pitch_c, offset_u, offset_v)
+
+    @classmethod
+    def nv12(cls, pitch=None, offset_uv=0):
+        """Luma plane, then one plane U0 V0 U1 V1 ...; `pitch`: bytes between the rows of both planes."""
+        return cls(CHROMA_UV, 0, pitch or 0, pitch or 0, offset_uv)
+
+    @classmethod
+    def nv21(cls, pitch=None, offset_vu=0):
+        """NV12 with V first in every pair."""
+        return cls(CHROMA_VU, 0, pitch or 0, pitch or 0, offset_vu)
+
+    @classmethod
+    def p010(cls, pitch=None, offset_uv=0):
+        """NV12 of 16-bit words with the sample in the high bits: P010, P012 or P016 for input_bitdepth 10, 12 (any depth above 8)."""
+        return cls(CHROMA_UV, 1, pitch or 0, pitch or 0, offset_uv)
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -107,6 +140,15 @@ def lib():
         L.thor_hip_kat_depth_up.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_kat_depth_down.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_frame_sse_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
+        LP = C.POINTER(FrameLayout)
+        L.thor_hip_layout_bytes.restype = C.c_size_t
+        L.thor_hip_layout_bytes.argtypes = [C.c_void_p, LP]
+        L.thor_hip_layout_bytes_for.restype = C.c_size_t
+        L.thor_hip_layout_bytes_for.argtypes = [C.c_int, C.c_int, C.c_int, LP]
+        L.thor_hip_stage_frame_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, LP, C.c_int]
+        L.thor_hip_get_recon_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, LP, C.c_int]
+        L.thor_hip_kat_layout_in.argtypes = [C.c_void_p, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_kat_layout_out.argtypes = [C.c_void_p, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -149,16 +191,36 @@ class Encoder:
             lib().thor_hip_close(self.h)
             self.h = None
 
-    def stage(self, stream, slot, frame):
+    def layout_bytes(self, layout):
+        """Bytes a frame in `layout` (a FrameLayout) spans; raises for a layout the library refuses."""
+        n = lib().thor_hip_layout_bytes(self.h, C.byref(layout))
+        if not n:
+            raise ValueError('frame layout refused (pitch below the row, pitch or offset no multiple of the sample size, msb_aligned with 8-bit input ...)')
+        return n
+
+    def stage(self, stream, slot, frame, layout=None):
+        """Stage a host frame: packed planar 4:2:0 of input-depth samples, or, with a FrameLayout, layout_bytes(layout) bytes in that layout."""
         frame = np.ascontiguousarray(frame).view(np.uint8)
+        if layout is not None:
+            assert frame.size >= self.layout_bytes(layout)
+            rc = lib().thor_hip_stage_frame_layout(self.h, stream, slot, frame.ctypes.data_as(C.c_void_p), C.byref(layout), 0)
+            if rc:
+                raise RuntimeError(f'thor_hip_stage_frame_layout rc={rc}')
+            return
         assert frame.size == self.frame_bytes
         rc = lib().thor_hip_stage_frame(self.h, stream, slot, frame.ctypes.data_as(C.c_void_p))
         if rc:
             raise RuntimeError(f'thor_hip_stage_frame rc={rc}')
 
-    def stage_device(self, stream, slot, dev_ptr):
+    def stage_device(self, stream, slot, dev_ptr, layout=None):
         """Stage a frame that already lives in HBM (device pointer to a contiguous planar 4:2:0 frame of input-depth samples; 16-byte aligned
-        when input_bitdepth < bitdepth)."""
+        when input_bitdepth < bitdepth).  With a FrameLayout: device pointer to a frame in that layout (NV12, P010, a row pitch ...), read by
+        the kernel that writes the slot; sample-aligned is enough."""
+        if layout is not None:
+            rc = lib().thor_hip_stage_frame_layout(self.h, stream, slot, C.c_void_p(dev_ptr), C.byref(layout), 1)
+            if rc:
+                raise RuntimeError(f'thor_hip_stage_frame_layout rc={rc}')
+            return
         rc = lib().thor_hip_stage_frame_device(self.h, stream, slot, C.c_void_p(dev_ptr))
         if rc:
             raise RuntimeError(f'thor_hip_stage_frame_device rc={rc}')
@@ -234,13 +296,27 @@ class Encoder:
         n = lib().thor_hip_stream_bytes(self.h, stream)
         return C.string_at(lib().thor_hip_stream_data(self.h, stream), n)
 
-    def recon(self, stream):
-        """Reconstruction of the stream's last coded frame: frame_bytes bytes (view them as self.dtype for the samples)."""
+    def recon(self, stream, layout=None):
+        """Reconstruction of the stream's last coded frame: frame_bytes bytes (view them as self.dtype for the samples); with a FrameLayout,
+        layout_bytes(layout) bytes in that layout (row padding and gaps between planes are zero)."""
+        if layout is not None:
+            out = np.zeros(self.layout_bytes(layout), dtype=np.uint8)
+            rc = lib().thor_hip_get_recon_layout(self.h, stream, out.ctypes.data_as(C.c_void_p), C.byref(layout), 0)
+            if rc:
+                raise RuntimeError(f'thor_hip_get_recon_layout rc={rc}')
+            return out
         out = np.empty(self.frame_bytes, dtype=np.uint8)
         rc = lib().thor_hip_get_recon(self.h, stream, out.ctypes.data_as(C.c_void_p))
         if rc:
             raise RuntimeError(f'thor_hip_get_recon rc={rc}')
         return out
+
+    def recon_device(self, stream, dev_ptr, layout):
+        """Reconstruction of the stream's last coded frame into device memory (layout_bytes(layout) bytes at dev_ptr) in `layout`; only the
+        picture's samples are written.  Synchronous at return."""
+        rc = lib().thor_hip_get_recon_layout(self.h, stream, C.c_void_p(dev_ptr), C.byref(layout), 1)
+        if rc:
+            raise RuntimeError(f'thor_hip_get_recon_layout rc={rc}')
 
     def recon_into(self, stream, ptr):
         """Reconstruction of the stream's last frame into a caller-owned host buffer of frame_bytes bytes (e.g. pinned memory that is reused)."""
@@ -558,3 +634,26 @@ def frame_sse_depth(a, b, width, height, bitdepth, input_bitdepth):
     out = (C.c_ulonglong * 3)()
     _kat('thor_hip_frame_sse_depth', _vp(a), _vp(b), width, height, bitdepth, input_bitdepth, out)
     return [int(v) for v in out]
+
+
+def layout_bytes(layout, width, height, input_bitdepth):
+    """thor_hip_layout_bytes_for: bytes a width x height frame in `layout` spans, 0 if the layout is refused.  Needs no encoder and no device."""
+    return lib().thor_hip_layout_bytes_for(width, height, input_bitdepth, C.byref(layout))
+
+
+def kat_layout_in(src, layout, width, height, input_bitdepth, bitdepth):
+    """thor_hip_kat_layout_in: a frame in `layout` (a uint8 array of at least layout_bytes; its address decides the kernel's path) through
+    k_layout_in -> packed planar 4:2:0 at `bitdepth`."""
+    assert src.dtype == np.uint8 and src.flags.c_contiguous and src.size >= layout_bytes(layout, width, height, input_bitdepth) > 0
+    out = np.zeros(width * height * 3 // 2, dtype=_pix(bitdepth))
+    _kat('thor_hip_kat_layout_in', _vp(src), C.byref(layout), width, height, input_bitdepth, bitdepth, _vp(out))
+    return out
+
+
+def kat_layout_out(planar, layout, width, height, input_bitdepth, bitdepth, dst):
+    """thor_hip_kat_layout_out: a packed planar 4:2:0 frame at `bitdepth` through k_layout_out into `dst`, in place: a uint8 array of layout_bytes
+    + 64 guard bytes, all of which travel to the device and back."""
+    a = _depth_frame(planar, bitdepth, width, height)
+    assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.size == layout_bytes(layout, width, height, input_bitdepth) + 64 > 64
+    _kat('thor_hip_kat_layout_out', _vp(a), C.byref(layout), width, height, input_bitdepth, bitdepth, _vp(dst))
+    return dst

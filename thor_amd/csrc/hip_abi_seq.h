@@ -75,6 +75,12 @@ static int unsupported(const SeqParams& s) {
   return 0;
 }
 
+// The caller's layout against a width x height picture of input_bitdepth samples; false: refused (a wrong `size` included).  Touches no device.
+static bool layout_resolved(const thor_hip_frame_layout* l, int width, int height, int input_bitdepth, PixLayout& L) {
+  if (!l || l->size != (int)sizeof(thor_hip_frame_layout)) return false;
+  return resolve_layout(l->chroma, l->msb_aligned, l->pitch_y, l->pitch_c, l->offset_u, l->offset_v, width, height, input_bitdepth, L);
+}
+
 extern "C" {
 
 int thor_hip_params_from_config(thor_hip_params* p, const char* cfg_path) {
@@ -102,7 +108,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1) return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420") return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -313,6 +319,45 @@ size_t thor_hip_frame_bytes(const thor_hip_encoder* e) {
 int thor_hip_get_recon(thor_hip_encoder* e, int stream, void* yuv_out) {
   if (!e || stream < 0 || stream >= e->S || !yuv_out) return 1;
   ENC_DISPATCH(e, { E.eng.download_rec(stream, yuv_out); });
+  return 0;
+}
+
+// ---- frames in a caller's layout (NV12 / NV21 / P010 ..., a row pitch): tk_filters.h PixLayout, k_layout_in / k_layout_out ----
+size_t thor_hip_layout_bytes_for(int width, int height, int input_bitdepth, const thor_hip_frame_layout* layout) {
+  PixLayout L;
+  if (width < 16 || height < 16 || width % 8 || height % 8 || (input_bitdepth != 8 && input_bitdepth != 10 && input_bitdepth != 12)) return 0;
+  return layout_resolved(layout, width, height, input_bitdepth, L) ? L.bytes : 0;
+}
+size_t thor_hip_layout_bytes(const thor_hip_encoder* e, const thor_hip_frame_layout* layout) {
+  return e ? thor_hip_layout_bytes_for(e->sp.width, e->sp.height, e->sp.input_bitdepth, layout) : 0;
+}
+int thor_hip_stage_frame_layout(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_frame_layout* layout, int on_device) {
+  PixLayout L;
+  if (!e || stream < 0 || stream >= e->S || slot < 0 || !frame) return 1;
+  if (!layout_resolved(layout, e->sp.width, e->sp.height, e->sp.input_bitdepth, L) || (uintptr_t)frame % (e->sp.input_bitdepth > 8 ? 2 : 1)) return 1;
+  ENC_DISPATCH(e, {
+    auto& v = E.staged[stream];
+    if ((int)v.size() <= slot) v.resize(slot + 1);
+    if (!v[slot].base_y) v[slot].alloc(e->sp.width, e->sp.height, 0);
+    if (on_device) {  // the kernel reads the caller's buffer and writes the slot
+      E.eng.layout_in(frame, L, v[slot].p);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+    } else
+      E.eng.stage_layout_host(frame, L, v[slot].p);
+  });
+  return 0;
+}
+int thor_hip_get_recon_layout(thor_hip_encoder* e, int stream, void* frame, const thor_hip_frame_layout* layout, int on_device) {
+  PixLayout L;
+  if (!e || stream < 0 || stream >= e->S || !frame) return 1;
+  if (!layout_resolved(layout, e->sp.width, e->sp.height, e->sp.input_bitdepth, L) || (uintptr_t)frame % (e->sp.input_bitdepth > 8 ? 2 : 1)) return 1;
+  ENC_DISPATCH(e, {
+    if (on_device) {
+      E.eng.layout_out(E.eng.st[stream].rec.p, frame, L);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+    } else
+      E.eng.fetch_layout_host(E.eng.st[stream].rec.p, frame, L);
+  });
   return 0;
 }
 void thor_hip_kernel_time(thor_hip_encoder*, double* sb_ms, long* sb_launches, double* filter_ms) {

@@ -349,6 +349,27 @@ void launch_frame_sse_depth(const FrameJob<uint16_t>* jobs, const FrameJob<uint1
   HIPCHECK(hipGetLastError());
 }
 
+// A frame in a caller's layout <-> the engine's planes, on g_stream (tk_encoder.h declares them).  `frame`: device memory, L.bytes of it.
+static dim3 layout_grid(int height) { return dim3((height + height / 2 + 3) / 4); }   // luma rows and chroma rows, four wavefronts per workgroup
+template <typename PIX> void launch_layout_in(const void* frame, const PixLayout& L, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth) {
+  const int up = bitdepth - input_bitdepth;
+  if constexpr (sizeof(PIX) == 1) hipLaunchKernelGGL((k_layout_in<uint8_t, uint8_t>), layout_grid(height), dim3(256), 0, g_stream, frame, L, dst, width, height, up);
+  else if (input_bitdepth == 8) hipLaunchKernelGGL((k_layout_in<uint8_t, uint16_t>), layout_grid(height), dim3(256), 0, g_stream, frame, L, dst, width, height, up);
+  else hipLaunchKernelGGL((k_layout_in<uint16_t, uint16_t>), layout_grid(height), dim3(256), 0, g_stream, frame, L, dst, width, height, up);
+  HIPCHECK(hipGetLastError());
+}
+template <typename PIX> void launch_layout_out(const Plane3<PIX>& src, void* frame, const PixLayout& L, int width, int height, int bitdepth, int input_bitdepth) {
+  const int shift = bitdepth - input_bitdepth;
+  if constexpr (sizeof(PIX) == 1) hipLaunchKernelGGL((k_layout_out<uint8_t, uint8_t>), layout_grid(height), dim3(256), 0, g_stream, src, frame, L, width, height, shift, input_bitdepth);
+  else if (input_bitdepth == 8) hipLaunchKernelGGL((k_layout_out<uint16_t, uint8_t>), layout_grid(height), dim3(256), 0, g_stream, src, frame, L, width, height, shift, input_bitdepth);
+  else hipLaunchKernelGGL((k_layout_out<uint16_t, uint16_t>), layout_grid(height), dim3(256), 0, g_stream, src, frame, L, width, height, shift, input_bitdepth);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_layout_in<uint8_t>(const void*, const PixLayout&, const Plane3<uint8_t>&, int, int, int, int);
+template void launch_layout_in<uint16_t>(const void*, const PixLayout&, const Plane3<uint16_t>&, int, int, int, int);
+template void launch_layout_out<uint8_t>(const Plane3<uint8_t>&, void*, const PixLayout&, int, int, int, int);
+template void launch_layout_out<uint16_t>(const Plane3<uint16_t>&, void*, const PixLayout&, int, int, int, int);
+
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {
 // Owning device array of n elements, zeroed (dev_alloc clears), filled from `h` when given; freed with its scope.

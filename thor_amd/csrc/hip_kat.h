@@ -672,6 +672,52 @@ extern "C" int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int
   fa.release(); fb.release();
   return 0;
 }
+// The two kernels behind thor_hip_stage_frame_layout / thor_hip_get_recon_layout on host buffers.  The device copy of the layout buffer starts as far off a
+// 16-byte boundary as the host buffer does, so the caller chooses between the kernels' vector and sample-by-sample paths with the pointer it passes.
+static int kat_layout_args(const void* lay, const void* planar, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, PixLayout& L) {
+  auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };
+  if (!lay || !planar || w % 8 || h % 8 || w < 16 || h < 16 || !ok(bitdepth) || !ok(input_bitdepth) || input_bitdepth > bitdepth) return 1;
+  return !layout_resolved(layout, w, h, input_bitdepth, L) || (uintptr_t)lay % (input_bitdepth > 8 ? 2 : 1);
+}
+static const size_t kKatLayoutGuard = 64;  // bytes after the layout that travel with thor_hip_kat_layout_out's dst
+template <typename PIX> static void kat_layout_in(const void* src, const PixLayout& L, int w, int h, int input_bitdepth, int bitdepth, PIX* out) {
+  const size_t skew = (uintptr_t)src & 15;
+  DevBuf<uint8_t> d(L.bytes + 16);
+  backend::h2d(d.p + skew, src, L.bytes);
+  DevFrame<PIX> f;
+  f.alloc(w, h, 0);
+  launch_layout_in<PIX>(d.p + skew, L, f.p, w, h, bitdepth, input_bitdepth);
+  backend::dev_sync();
+  download_yuv(f, out, w, h);
+  f.release();
+}
+template <typename PIX> static void kat_layout_out(const PIX* in, const PixLayout& L, int w, int h, int input_bitdepth, int bitdepth, void* dst) {
+  const size_t skew = (uintptr_t)dst & 15;
+  DevBuf<uint8_t> d(L.bytes + kKatLayoutGuard + 16);
+  backend::h2d(d.p + skew, dst, L.bytes + kKatLayoutGuard);
+  DevFrame<PIX> f;
+  f.alloc(w, h, 0);
+  upload_yuv(f, in, w, h);
+  launch_layout_out<PIX>(f.p, d.p + skew, L, w, h, bitdepth, input_bitdepth);
+  backend::d2h(dst, d.p + skew, L.bytes + kKatLayoutGuard);
+  f.release();
+}
+extern "C" int thor_hip_kat_layout_in(const void* src, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* planar_out) {
+  PixLayout L;
+  if (kat_layout_args(src, planar_out, layout, w, h, input_bitdepth, bitdepth, L)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_layout_in<uint8_t>(src, L, w, h, input_bitdepth, bitdepth, (uint8_t*)planar_out);
+  else kat_layout_in<uint16_t>(src, L, w, h, input_bitdepth, bitdepth, (uint16_t*)planar_out);
+  return 0;
+}
+extern "C" int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* dst) {
+  PixLayout L;
+  if (kat_layout_args(dst, planar_in, layout, w, h, input_bitdepth, bitdepth, L)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_layout_out<uint8_t>((const uint8_t*)planar_in, L, w, h, input_bitdepth, bitdepth, dst);
+  else kat_layout_out<uint16_t>((const uint16_t*)planar_in, L, w, h, input_bitdepth, bitdepth, dst);
+  return 0;
+}
 extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
   KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),
          kat_interpolate<uint16_t>((const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, (uint16_t*)out_yuv));

@@ -1,6 +1,6 @@
 // hip_kernels.h - the frame-level kernels of the throughput build (part of the translation unit thor_hip.cpp, device-only): deblocking, padded
 // reference, frame SSE, bit gather, CDEF, CLPF, the temporally interpolated reference, the bit-depth conversion of frames that enter and leave at a lower
-// input depth.  Launched by hip_backend.h.
+// input depth, the conversion between a caller's frame layout (NV12, P010, a row pitch) and the engine's planes.  Launched by hip_backend.h.
 // The dependency-driven persistent superblock kernel is not here: a task is (stream, superblock), SB(k,l) needs its left neighbour (k,l-1) and its
 // up-right neighbour (k-1,l+1) ((k-1,l) in the last column) - SURVEY.md Appendix A; the kernel is in tk_kernel.h, its ready-task queue in tk_sched.h.
 #pragma once
@@ -204,5 +204,18 @@ __global__ __launch_bounds__(256) void k_frame_sse_depth(const FrameJob<uint16_t
     const unsigned long long v = wave_sum64_dpp(acc[k]);
     if (lane == 0 && v) atomicAdd(&out[4 * (size_t)blockIdx.y + k], v);
   }
+}
+
+// ---- frames in a caller's layout (tk_filters.h: layout_in_rows, layout_out_rows) --------
+// One frame per launch, one wavefront per luma or chroma row, lanes along the row, as above.  `frame`: device memory in layout L.
+template <typename SRC, typename PIX>
+__global__ __launch_bounds__(256) void k_layout_in(const void* frame, PixLayout L, Plane3<PIX> dst, int width, int height, int up) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  layout_in_rows<SRC, PIX>(frame, L, dst, width, height, up, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64);
+}
+template <typename PIX, typename DST>
+__global__ __launch_bounds__(256) void k_layout_out(Plane3<PIX> src, void* frame, PixLayout L, int width, int height, int shift, int input_bitdepth) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  layout_out_rows<PIX, DST>(src, frame, L, width, height, shift, input_bitdepth, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64);
 }
 }  // namespace tk

@@ -19,6 +19,7 @@ struct CliArgs {
   int num_frames = 600, skip = 0, streams = 1;
   int snrcalc = 1;           // -snrcalc (enc/strings.c:340): PSNR of every frame in the report
   std::string statfile;      // -stat FILE: one summary line per stream appended (enc/mainenc.c:652-667)
+  std::string pixfmt = "i420";  // -pixfmt i420|nv12|nv21|p010: layout of the -if and -rf files (tight rows; not an option of the reference)
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -55,6 +56,10 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
     else if (k == "-streams") a.streams = I();
     else if (k == "-snrcalc") a.snrcalc = I();
     else if (k == "-stat") a.statfile = v;
+    else if (k == "-pixfmt") {
+      a.pixfmt = v;
+      if (v != "i420" && v != "nv12" && v != "nv21" && v != "p010" && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
     else if (k == "-width") p.width = I();
     else if (k == "-height") p.height = I();
     else if (k == "-qp") p.qp = I();
@@ -142,12 +147,25 @@ static inline CliArgs cli_parse(int argc, char** argv) {
   return a;
 }
 
+// -pixfmt as a tight layout of a width x height picture: nv12 / nv21 interleave the chroma samples, p010 does so with the samples in the high bits
+// of 16-bit words (any input depth above 8).  false: the format cannot hold input of this depth (p010 with 8-bit input).
+static inline bool cli_pixfmt_layout(const std::string& pixfmt, int width, int height, int input_bitdepth, PixLayout& L) {
+  const int chroma = pixfmt == "i420" ? 0 : pixfmt == "nv21" ? 2 : 1;
+  return resolve_layout(chroma, pixfmt == "p010", 0, 0, 0, 0, width, height, input_bitdepth, L);
+}
+
 // Encode `num_frames` frames of a raw 4:2:0 file with S identical-geometry streams: stream s
 // codes frames [skip + s*num_frames, skip + (s+1)*num_frames) as its own closed stream (what the
 // reference produces with -skip/-n).  Outputs "<of>" for S==1, "<of>.<s>" otherwise.
 // stdout: the reference's report (tk_report.h); with S > 1 every stream's, in stream order, each after a line "stream <s>".
 template <typename PIX> int cli_run(const CliArgs& a) {
   const SeqParams& p = a.sp;
+  PixLayout lay;
+  const bool use_layout = a.pixfmt != "i420";   // i420 is the path the files always took
+  if (!cli_pixfmt_layout(a.pixfmt, p.width, p.height, p.input_bitdepth, lay)) {
+    fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", a.pixfmt.c_str());
+    return 2;
+  }
   FILE* fi = fopen(a.infile.c_str(), "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", a.infile.c_str()); return 2; }
   Engine<PIX> eng;
@@ -164,6 +182,8 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   const int file_frames = (int)(ftell(fi) / (long)fsz);
   for (int s = 0; s < a.streams; s++) eng.begin_sequence(s, a.skip + s * a.num_frames, a.num_frames, file_frames);
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
+  auto upload = [&](int s) { if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
+  auto download = [&](int s) { if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
   // THOR_STAGGER=1 (tests): the streams in two groups half a frame apart (Engine::encode_run) instead of lock step
   if (getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER")) && a.streams > 1) {
     int rc = 0;
@@ -172,12 +192,12 @@ template <typename PIX> int cli_run(const CliArgs& a) {
           if (!eng.schedule(s)) return false;
           const size_t idx = (size_t)eng.st[s].cur_abs;
           if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); rc = 3; return false; }
-          eng.upload_orig(s, frame.data());
+          upload(s);
           return true;
         },
         [&](int first, int count) {
           for (int s = first; s < first + count; s++)
-            if (fr[s]) { eng.download_rec(s, rec.data()); recs[(size_t)s * a.num_frames + eng.st[s].cur.frame_num] = rec; }
+            if (fr[s]) { download(s); recs[(size_t)s * a.num_frames + eng.st[s].cur.frame_num] = rec; }
         });
     if (rc) return rc;
   } else
@@ -192,7 +212,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
         fprintf(stderr, "short read at frame %zu\n", idx);
         return 3;
       }
-      eng.upload_orig(s, frame.data());
+      upload(s);
       fp[s] = eng.st[s].cur;
     }
     if (!active) break;
@@ -214,7 +234,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
     }
     for (int s = 0; s < a.streams; s++)
       if (fr[s]) {
-        eng.download_rec(s, rec.data());
+        download(s);
         recs[(size_t)s * a.num_frames + fp[s].frame_num] = rec;
       }
   }

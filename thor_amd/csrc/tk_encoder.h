@@ -69,6 +69,10 @@ template <typename PIX> void launch_frame_sse(const FrameJob<PIX>* jobs, const F
 void launch_depth_up(const void* packed, const Plane3<uint16_t>& dst, int width, int height, int bitdepth, int input_bitdepth);
 void launch_depth_down(const Plane3<uint16_t>& src, void* packed, int width, int height, int bitdepth, int input_bitdepth);
 void launch_frame_sse_depth(const FrameJob<uint16_t>* jobs, const FrameJob<uint16_t>* hjobs, int S, int bitdepth, int input_bitdepth, unsigned long long* out);
+// A frame in a caller's layout (tk_filters.h: PixLayout, layout_in_rows, layout_out_rows) <-> planes at the engine's depth, one launch each on the
+// library's stream.  `frame`: device memory.  The host build calls the row functions directly (Engine::layout_in / layout_out).
+template <typename PIX> void launch_layout_in(const void* frame, const PixLayout& L, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth);
+template <typename PIX> void launch_layout_out(const Plane3<PIX>& src, void* frame, const PixLayout& L, int width, int height, int bitdepth, int input_bitdepth);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -414,6 +418,8 @@ template <typename PIX> class Engine {
   bool frame_distortion = false;        // measure the per-plane SSE of every coded frame (off: a frame's launches and copies are unchanged)
   unsigned long long* d_sse = nullptr;  // [S][4]: Y, U, V sums of the frame just finished (allocated on first use)
   void* d_packed = nullptr;             // input_bitdepth < bitdepth: one packed frame of input-depth samples, staging for upload_orig / download_rec
+  void* d_layout = nullptr;             // a host frame in a caller's layout, as it came (stage_layout_host / fetch_layout_host); allocated on first use
+  size_t d_layout_bytes = 0;
 
   // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
   int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
@@ -526,6 +532,7 @@ template <typename PIX> class Engine {
     backend::dev_free(d_ijobs); d_ijobs = nullptr;
     backend::dev_free(d_sse); d_sse = nullptr;
     backend::dev_free(d_packed); d_packed = nullptr;
+    backend::dev_free(d_layout); d_layout = nullptr; d_layout_bytes = 0;
   }
 
   // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
@@ -548,6 +555,57 @@ template <typename PIX> class Engine {
 #else
       launch_depth_down(src, packed, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
 #endif
+    }
+  }
+
+  // A frame in a caller's layout (tk_filters.h: PixLayout; input-depth samples) in device memory -> planes at the engine's depth, and planes -> such a
+  // frame: one kernel, no intermediate frame.  Asynchronous on the device: ordered with the engine's other work.
+  void layout_in(const void* frame, const PixLayout& L, const Plane3<PIX>& dst) {
+#if TK_HOST
+    if constexpr (sizeof(PIX) == 1) layout_in_rows<uint8_t, PIX>(frame, L, dst, sp.width, sp.height, 0, 0, 1, 0, 1);
+    else if (sp.input_bitdepth == 8) layout_in_rows<uint8_t, PIX>(frame, L, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+    else layout_in_rows<uint16_t, PIX>(frame, L, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+#else
+    launch_layout_in<PIX>(frame, L, dst, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+  }
+  void layout_out(const Plane3<PIX>& src, void* frame, const PixLayout& L) {
+#if TK_HOST
+    if constexpr (sizeof(PIX) == 1) layout_out_rows<PIX, uint8_t>(src, frame, L, sp.width, sp.height, 0, sp.input_bitdepth, 0, 1, 0, 1);
+    else if (sp.input_bitdepth == 8) layout_out_rows<PIX, uint8_t>(src, frame, L, sp.width, sp.height, depth_shift(), sp.input_bitdepth, 0, 1, 0, 1);
+    else layout_out_rows<PIX, uint16_t>(src, frame, L, sp.width, sp.height, depth_shift(), sp.input_bitdepth, 0, 1, 0, 1);
+#else
+    launch_layout_out<PIX>(src, frame, L, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+  }
+  // The caller's description of a layout against this engine's pictures; false: refused (needs no device).
+  bool resolve(int chroma, int msb_aligned, long long pitch_y, long long pitch_c, size_t off_u, size_t off_v, PixLayout& L) const {
+    return resolve_layout(chroma, msb_aligned, pitch_y, pitch_c, off_u, off_v, sp.width, sp.height, sp.input_bitdepth, L);
+  }
+  // The same for a frame in host memory: its bytes travel once, as they are, into a device buffer (allocated on first use, grown when a larger layout
+  // comes) and the same kernel runs.  Synchronous like upload_orig / download_rec.
+  void* layout_buf(size_t bytes) {
+    if (bytes > d_layout_bytes) { backend::dev_sync(); backend::dev_free(d_layout); d_layout = backend::dev_alloc(bytes); d_layout_bytes = bytes; }
+    return d_layout;
+  }
+  void stage_layout_host(const void* frame, const PixLayout& L, const Plane3<PIX>& dst) {
+    backend::h2d(layout_buf(L.bytes), frame, L.bytes);
+    layout_in(d_layout, L, dst);
+    backend::dev_sync();
+  }
+  // Only the picture's bytes of `frame` are written: a tight layout arrives with one copy; with a pitch or gaps the rows are cut out of a host copy
+  // of the device buffer, as download_rec cuts them out of padded planes.
+  void fetch_layout_host(const Plane3<PIX>& src, void* frame, const PixLayout& L) {
+    layout_out(src, layout_buf(L.bytes), L);
+    if (L.bytes == frame_bytes()) { backend::d2h(frame, d_layout, L.bytes); return; }
+    std::vector<uint8_t> tmp(L.bytes);
+    backend::d2h(tmp.data(), d_layout, L.bytes);
+    const size_t B = sp.input_bitdepth > 8 ? 2 : 1, row_y = sp.width * B, row_c = L.chroma == 0 ? row_y / 2 : row_y;
+    uint8_t* out = (uint8_t*)frame;
+    for (int i = 0; i < sp.height; i++) memcpy(out + i * L.pitch_y, &tmp[i * L.pitch_y], row_y);
+    for (int i = 0; i < sp.height / 2; i++) {
+      memcpy(out + L.off_u + i * L.pitch_c, &tmp[L.off_u + i * L.pitch_c], row_c);
+      if (L.chroma == 0) memcpy(out + L.off_v + i * L.pitch_c, &tmp[L.off_v + i * L.pitch_c], row_c);
     }
   }
 

@@ -269,4 +269,154 @@ TK_DEV void frame_sse_depth_rows(const Plane3<uint16_t>& org, const Plane3<uint1
   }
 }
 
+// ---- frames in a caller's layout: semi-planar chroma, a row pitch, samples in the high bits (include/thor_hip.h: thor_hip_frame_layout) ------
+// What decoders, capture cards and GPU pipelines hand over: NV12 / NV21 for 8 bits, P010 / P012 / P016 above.  The same pass applies the depth
+// conversion of the section above, so such a frame becomes the engine's planes, or the reconstruction such a frame, with one read and one write of
+// every sample.  Bytes of a row beyond the picture and bytes between planes are neither read nor written.
+struct PixLayout {  // a layout resolved against a picture (resolve_layout): no zero left that means "tight", everything in bytes
+  int chroma;       // 0: U and V planes, 1: one plane U0 V0 U1 V1 ..., 2: V0 U0 V1 U1 ...
+  int msb;          // samples are value << msb (16 - input_bitdepth for P010 / P012 / P016, else 0)
+  size_t pitch_y, pitch_c, off_u, off_v;
+  size_t bytes;     // from the base to the end of the last row's pitch: what a buffer in this layout holds
+};
+
+// The caller's description (0 = tight / adjacent) against a width x height 4:2:0 picture of input_bitdepth samples.  false: the layout is refused.
+static inline bool resolve_layout(int chroma, int msb_aligned, long long pitch_y, long long pitch_c, size_t off_u, size_t off_v, int width, int height,
+                                  int input_bitdepth, PixLayout& L) {
+  const size_t B = input_bitdepth > 8 ? 2 : 1;
+  if (chroma < 0 || chroma > 2 || msb_aligned < 0 || msb_aligned > 1 || (msb_aligned && input_bitdepth <= 8)) return false;
+  const size_t row_y = (size_t)width * B, row_c = chroma == 0 ? row_y / 2 : row_y;
+  if (pitch_y < 0 || pitch_c < 0) return false;
+  L.chroma = chroma;
+  L.msb = msb_aligned ? 16 - input_bitdepth : 0;
+  L.pitch_y = pitch_y ? (size_t)pitch_y : row_y;
+  L.pitch_c = pitch_c ? (size_t)pitch_c : row_c;
+  if (L.pitch_y < row_y || L.pitch_c < row_c || L.pitch_y % B || L.pitch_c % B || off_u % B || off_v % B) return false;
+  const size_t rows_c = (size_t)height / 2;
+  L.off_u = off_u ? off_u : L.pitch_y * height;
+  L.off_v = chroma == 0 ? (off_v ? off_v : L.off_u + L.pitch_c * rows_c) : 0;
+  L.bytes = L.pitch_y * height;
+  if (L.off_u + L.pitch_c * rows_c > L.bytes) L.bytes = L.off_u + L.pitch_c * rows_c;
+  if (chroma == 0 && L.off_v + L.pitch_c * rows_c > L.bytes) L.bytes = L.off_v + L.pitch_c * rows_c;
+  return true;
+}
+
+// N samples moved as one: 16 bytes on the layout side (one dwordx4), as much as that makes on the plane side.
+template <typename T, int N> struct alignas(N * sizeof(T) < 16 ? N * sizeof(T) : 16) LayoutVec { T v[N]; };
+
+template <typename SRC, typename PIX> TK_DEV PIX layout_in_sample(SRC s, int msb, int up) { return (PIX)((((int)s) >> msb) << up); }
+template <typename PIX, typename DST> TK_DEV DST layout_out_sample(PIX v, int shift, int maxv, int msb) {
+  const int r = shift > 0 ? depth_round((int)v, shift, maxv) : (int)v;
+  return (DST)(r << msb);
+}
+
+// One row of n samples, layout -> plane.  vec: `s` and its pitch are 16-byte aligned (plane rows always are); whole vectors first, the rest of
+// the row (n is a multiple of 4 only) sample by sample.
+template <typename SRC, typename PIX> TK_DEV void layout_in_run(const SRC* s, PIX* d, int n, int msb, int up, bool vec, int lane, int nlanes) {
+  constexpr int N = 16 / (int)sizeof(SRC);
+  const int nv = vec ? n / N : 0;
+  for (int i = lane; i < nv; i += nlanes) {
+    const LayoutVec<SRC, N> a = ((const LayoutVec<SRC, N>*)s)[i];
+    LayoutVec<PIX, N> o;
+    for (int k = 0; k < N; k++) o.v[k] = layout_in_sample<SRC, PIX>(a.v[k], msb, up);
+    ((LayoutVec<PIX, N>*)d)[i] = o;
+  }
+  for (int i = nv * N + lane; i < n; i += nlanes) d[i] = layout_in_sample<SRC, PIX>(s[i], msb, up);
+}
+// One row of n interleaved pairs -> rows d0 (first of each pair) and d1: a vector of pairs in, two half-width vectors out.
+template <typename SRC, typename PIX> TK_DEV void layout_in_pairs(const SRC* s, PIX* d0, PIX* d1, int n, int msb, int up, bool vec, int lane, int nlanes) {
+  constexpr int N = 8 / (int)sizeof(SRC);
+  const int nv = vec ? n / N : 0;
+  for (int i = lane; i < nv; i += nlanes) {
+    const LayoutVec<SRC, 2 * N> a = ((const LayoutVec<SRC, 2 * N>*)s)[i];
+    LayoutVec<PIX, N> o0, o1;
+    for (int k = 0; k < N; k++) { o0.v[k] = layout_in_sample<SRC, PIX>(a.v[2 * k], msb, up); o1.v[k] = layout_in_sample<SRC, PIX>(a.v[2 * k + 1], msb, up); }
+    ((LayoutVec<PIX, N>*)d0)[i] = o0;
+    ((LayoutVec<PIX, N>*)d1)[i] = o1;
+  }
+  for (int i = nv * N + lane; i < n; i += nlanes) { d0[i] = layout_in_sample<SRC, PIX>(s[2 * i], msb, up); d1[i] = layout_in_sample<SRC, PIX>(s[2 * i + 1], msb, up); }
+}
+// The two above the other way: plane -> layout, rounded back to the input depth when shift > 0.
+template <typename PIX, typename DST>
+TK_DEV void layout_out_run(const PIX* s, DST* d, int n, int shift, int maxv, int msb, bool vec, int lane, int nlanes) {
+  constexpr int N = 16 / (int)sizeof(DST);
+  const int nv = vec ? n / N : 0;
+  for (int i = lane; i < nv; i += nlanes) {
+    const LayoutVec<PIX, N> a = ((const LayoutVec<PIX, N>*)s)[i];
+    LayoutVec<DST, N> o;
+    for (int k = 0; k < N; k++) o.v[k] = layout_out_sample<PIX, DST>(a.v[k], shift, maxv, msb);
+    ((LayoutVec<DST, N>*)d)[i] = o;
+  }
+  for (int i = nv * N + lane; i < n; i += nlanes) d[i] = layout_out_sample<PIX, DST>(s[i], shift, maxv, msb);
+}
+template <typename PIX, typename DST>
+TK_DEV void layout_out_pairs(const PIX* s0, const PIX* s1, DST* d, int n, int shift, int maxv, int msb, bool vec, int lane, int nlanes) {
+  constexpr int N = 8 / (int)sizeof(DST);
+  const int nv = vec ? n / N : 0;
+  for (int i = lane; i < nv; i += nlanes) {
+    const LayoutVec<PIX, N> a0 = ((const LayoutVec<PIX, N>*)s0)[i], a1 = ((const LayoutVec<PIX, N>*)s1)[i];
+    LayoutVec<DST, 2 * N> o;
+    for (int k = 0; k < N; k++) { o.v[2 * k] = layout_out_sample<PIX, DST>(a0.v[k], shift, maxv, msb); o.v[2 * k + 1] = layout_out_sample<PIX, DST>(a1.v[k], shift, maxv, msb); }
+    ((LayoutVec<DST, 2 * N>*)d)[i] = o;
+  }
+  for (int i = nv * N + lane; i < n; i += nlanes) { d[2 * i] = layout_out_sample<PIX, DST>(s0[i], shift, maxv, msb); d[2 * i + 1] = layout_out_sample<PIX, DST>(s1[i], shift, maxv, msb); }
+}
+
+// Whether the rows that start at base + off and follow each other at `pitch` all lie on 16-byte boundaries.
+TK_DEV bool layout_rows_aligned(const void* base, size_t off, size_t pitch) { return ((((uintptr_t)base + off) | pitch) & 15) == 0; }
+
+// A frame at `base` in layout L (SRC = uint8_t for input depth 8, uint16_t otherwise) -> the engine's planes: x = s >> L.msb, plane sample x << up
+// (up = bitdepth - input_bitdepth, depth_up_rows' widening).  One work item per luma row, then one per chroma row (its U and its V samples);
+// `lane`/`nlanes` stride along the row.
+template <typename SRC, typename PIX>
+TK_DEV void layout_in_rows(const void* base, const PixLayout& L, const Plane3<PIX>& dst, int width, int height, int up, int gid, int gsize, int lane,
+                           int nlanes) {
+  const uint8_t* b = (const uint8_t*)base;
+  const bool vy = layout_rows_aligned(b, 0, L.pitch_y);
+  const bool vc = layout_rows_aligned(b, L.off_u, L.pitch_c) && (L.chroma != 0 || layout_rows_aligned(b, L.off_v, L.pitch_c));
+  const int total = height + height / 2;
+  for (int it = gid; it < total; it += gsize) {
+    if (it < height) {
+      layout_in_run((const SRC*)(b + (size_t)it * L.pitch_y), dst.y + (size_t)it * dst.sy, width, L.msb, up, vy, lane, nlanes);
+      continue;
+    }
+    const size_t r = (size_t)(it - height);
+    PIX* du = dst.u + r * dst.sc;
+    PIX* dv = dst.v + r * dst.sc;
+    const SRC* su = (const SRC*)(b + L.off_u + r * L.pitch_c);
+    if (L.chroma == 0) {
+      layout_in_run(su, du, width / 2, L.msb, up, vc, lane, nlanes);
+      layout_in_run((const SRC*)(b + L.off_v + r * L.pitch_c), dv, width / 2, L.msb, up, vc, lane, nlanes);
+    } else
+      layout_in_pairs(su, L.chroma == 1 ? du : dv, L.chroma == 1 ? dv : du, width / 2, L.msb, up, vc, lane, nlanes);
+  }
+}
+
+// The engine's planes -> a frame at `base` in layout L (DST = uint8_t for input depth 8, uint16_t otherwise): r = depth_round(v, shift, max) when
+// shift = bitdepth - input_bitdepth > 0, else v; written r << L.msb.  Same work split.
+template <typename PIX, typename DST>
+TK_DEV void layout_out_rows(const Plane3<PIX>& src, void* base, const PixLayout& L, int width, int height, int shift, int input_bitdepth, int gid, int gsize,
+                            int lane, int nlanes) {
+  uint8_t* b = (uint8_t*)base;
+  const int maxv = (1 << input_bitdepth) - 1;
+  const bool vy = layout_rows_aligned(b, 0, L.pitch_y);
+  const bool vc = layout_rows_aligned(b, L.off_u, L.pitch_c) && (L.chroma != 0 || layout_rows_aligned(b, L.off_v, L.pitch_c));
+  const int total = height + height / 2;
+  for (int it = gid; it < total; it += gsize) {
+    if (it < height) {
+      layout_out_run(src.y + (size_t)it * src.sy, (DST*)(b + (size_t)it * L.pitch_y), width, shift, maxv, L.msb, vy, lane, nlanes);
+      continue;
+    }
+    const size_t r = (size_t)(it - height);
+    const PIX* su = src.u + r * src.sc;
+    const PIX* sv = src.v + r * src.sc;
+    DST* du = (DST*)(b + L.off_u + r * L.pitch_c);
+    if (L.chroma == 0) {
+      layout_out_run(su, du, width / 2, shift, maxv, L.msb, vc, lane, nlanes);
+      layout_out_run(sv, (DST*)(b + L.off_v + r * L.pitch_c), width / 2, shift, maxv, L.msb, vc, lane, nlanes);
+    } else
+      layout_out_pairs(L.chroma == 1 ? su : sv, L.chroma == 1 ? sv : su, du, width / 2, shift, maxv, L.msb, vc, lane, nlanes);
+  }
+}
+
 }  // namespace tk

@@ -1,7 +1,10 @@
 /* thorenc_hip.c - minimal C front end over the libthor_hip.so sequence API (include/thor_hip.h).
  * Usage mirrors the reference Thorenc (enc/strings.c:287-356) for the options this path honours:
  *   thorenc_hip -cf config.txt -if in.yuv -width W -height H -qp Q -n N [-skip K] [-f fps]
- *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-name value ...]
+ *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-pixfmt i420|nv12|nv21|p010] [-name value ...]
+ * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
+ * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
+ * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -23,13 +26,16 @@ static double now_s(void) {
 }
 
 /* thor_hip_encode_staged_run's callback: keep the reconstructions of the frames that just completed (display order) */
-struct done_ctx { thor_hip_encoder* e; unsigned char** recs; FILE** fr; int n; size_t fsz; };
+struct done_ctx { thor_hip_encoder* e; unsigned char** recs; FILE** fr; int n; size_t fsz; const thor_hip_frame_layout* lay; };
+static void get_recon(thor_hip_encoder* e, int s, unsigned char* r, const thor_hip_frame_layout* lay) {
+  if (lay) thor_hip_get_recon_layout(e, s, r, lay, 0); else thor_hip_get_recon(e, s, r);
+}
 static void frames_done(void* user, int first, int count) {
   struct done_ctx* c = (struct done_ctx*)user;
   for (int s = first; s < first + count; s++)
     if (c->fr[s]) {
       unsigned char* r = (unsigned char*)malloc(c->fsz);
-      thor_hip_get_recon(c->e, s, r);
+      get_recon(c->e, s, r, c->lay);
       c->recs[(size_t)s * c->n + thor_hip_last_display_index(c->e, s)] = r;
     }
 }
@@ -38,6 +44,7 @@ int main(int argc, char** argv) {
   thor_hip_params p;
   const char *inf = NULL, *of = NULL, *rf = NULL;
   const char* statf = NULL;
+  const char* pixfmt = "i420";
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -54,6 +61,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-streams")) S = atoi(v);
     else if (!strcmp(k, "-snrcalc")) snrcalc = atoi(v);
     else if (!strcmp(k, "-stat")) statf = v;
+    else if (!strcmp(k, "-pixfmt")) pixfmt = v;
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -61,6 +69,13 @@ int main(int argc, char** argv) {
   FILE* fi = fopen(inf, "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", inf); return 2; }
   if (p.input_bitdepth > p.bitdepth) { fprintf(stderr, "Run-time error...\ninput_bitdepth %d above bitdepth %d is not implemented by this path\n...now exiting to system...\n", p.input_bitdepth, p.bitdepth); return 2; }
+  thor_hip_frame_layout layout = {sizeof(thor_hip_frame_layout), THOR_HIP_CHROMA_PLANAR, 0, 0, 0, 0, 0};
+  const thor_hip_frame_layout* lay = strcmp(pixfmt, "i420") ? &layout : NULL; /* i420: the calls the files always took */
+  if (!strcmp(pixfmt, "nv12")) layout.chroma = THOR_HIP_CHROMA_UV;
+  else if (!strcmp(pixfmt, "nv21")) layout.chroma = THOR_HIP_CHROMA_VU;
+  else if (!strcmp(pixfmt, "p010")) { layout.chroma = THOR_HIP_CHROMA_UV; layout.msb_aligned = 1; }
+  else if (lay) { fprintf(stderr, "Run-time error...\noption -pixfmt %s is unknown\n...now exiting to system...\n", pixfmt); return 2; }
+  if (lay && p.input_bitdepth <= 8 && layout.msb_aligned) { fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", pixfmt); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
   size_t fsz = thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth */
@@ -71,7 +86,7 @@ int main(int argc, char** argv) {
       size_t idx = (size_t)skip + (size_t)s * n + f;
       if (wrap > 0) idx %= (size_t)wrap;
       if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame, 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); return 4; }
-      thor_hip_stage_frame(e, s, f, frame);
+      if (lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
     }
   FILE** fr = (FILE**)calloc(S, sizeof(FILE*));
   char name[4096];
@@ -89,7 +104,7 @@ int main(int argc, char** argv) {
   double t0 = now_s(), tenc = 0;
   int coded = 0;
   if (S > 1 && getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER"))) {
-    struct done_ctx ctx = {e, recs, fr, n, fsz};
+    struct done_ctx ctx = {e, recs, fr, n, fsz, lay};
     double a = now_s();
     if (thor_hip_encode_staged_run(e, n, frames_done, &ctx)) { fprintf(stderr, "encode failed\n"); return 5; }
     tenc = now_s() - a;
@@ -107,7 +122,7 @@ int main(int argc, char** argv) {
     for (int s = 0; s < S; s++)
       if (fr[s]) {
         unsigned char* r = (unsigned char*)malloc(fsz);
-        thor_hip_get_recon(e, s, r);
+        get_recon(e, s, r, lay);
         recs[(size_t)s * n + slots[s]] = r;
       }
   }
