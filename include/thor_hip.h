@@ -276,6 +276,15 @@ int thor_hip_kat_cdef_dir(const void* blocks, int bitdepth, int n, int* dir, int
 /* cdef_filter_block (common/common_block.c:224-279) of `n` bsize x bsize blocks (8 luma, 4 chroma) of a plane; samples outside the plane count as
  * CDEF_VERY_LARGE (cdef_prepare_input, common/common_frame.c:766).  par[7*i..]: x0, y0, pri_strength, sec_strength, dir, pri_damping, sec_damping. */
 int thor_hip_kat_cdef_filter(const void* plane, int width, int height, int stride, int bitdepth, int bsize, int n, const int* par, void* out);
+/* The CDEF strength search and frame filter (cdef_search + cdef_frame for the three planes, enc/encode_frame.c:228-489, :768-774, common/common_frame.c:826-1003)
+ * of `n_jobs` frames of one size through the encoder's own launch sequence (copy, flags, direction / variance, distortions, joint strength selection, apply -
+ * one launch each for all jobs).  rec_yuv / org_yuv: n_jobs packed planar 4:2:0 frames (deblocked / original); mode: per job (height / 4) x (width / 4)
+ * block_mode_t bytes; qp, speed, cdef_bits: one entry per job - speed = -cdef minus 1 (0..2), cdef_bits the frame-level guess (0 = fixed strengths from qp); damping 5.  Returned per job: dir (int8) and
+ * var per 8x8 luma block in raster order (0 where the passes wrote none); fb_compact per 64x64 filter block (its index among the live ones or -1); mse
+ * [2][filter blocks][64]; result = 34 ints: nb_bits, strengths[8], uv_strengths[8], sb_count, 16 ints of scratch; fb_sel per filter block (the preset chosen);
+ * out_yuv: the filtered frames.  width, height: multiples of 8, at least 8; qp 0..51; cdef_bits 0..3.  Known answers: tests/golden/gen_kat10.py -> kat10.npz. */
+int thor_hip_kat_cdef_frame(int n_jobs, const void* rec_yuv, const void* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, const int* qp,
+                            const int* speed, const int* cdef_bits, int8_t* dir, int* var, int* fb_compact, unsigned long long* mse, int* result, int* fb_sel, void* out_yuv);
 /* CLPF on one planar 4:2:0 frame: the per-8x8-block squared errors of detect_multi_clpf (enc/encode_block.c:2556-2621; stats[4*b..]: unfiltered,
  * strength 1, 2, 4; blocks in luma raster order, then U, then V; a block whose top-left cell is skip-coded reports {0, 0xffffffff, 0, 0}) and the
  * filtered frame of clpf_frame / clpf_block (common/common_frame.c:1005-1163, common/common_block.c:325-345) for the given per-plane strengths

@@ -3,14 +3,18 @@
  * copied into this repository) to reach its file-static kernels, and exports thin wrappers so that
  * tests/golden/gen_kat*.py can record known-answer vectors from the real reference code.
  * -DREFSHIM_HBD: the 16-bit build of the same file (enc/encode_block_hbd.c by path) with the two motion-search
- * wrappers only, suffixed _hbd; linked into a shared object of its own (libthorref_hbd.so). */
+ * wrappers and the two CDEF entries only, suffixed _hbd; linked into a shared object of its own (libthorref_hbd.so).
+ * enc/encode_frame.c (encode_frame_hbd.c) is included the same way, for its file-static dist_8x8: the two shared objects take the functions of that file from
+ * this translation unit instead of encode_frame.o / encode_frame_hbd.o. */
 #define STR2(x) #x
 #define STR(x) STR2(x)
 #ifdef REFSHIM_HBD
 #include STR(REFDIR/enc/encode_block_hbd.c)
+#include STR(REFDIR/enc/encode_frame_hbd.c)
 #define SHIM(name) name##_hbd
 #else
 #include STR(REFDIR/enc/encode_block.c)
+#include STR(REFDIR/enc/encode_frame.c)
 #define SHIM(name) name
 #endif
 #include "simd.h"
@@ -53,6 +57,150 @@ int SHIM(ref_motion_estimate_bi)(SAMPLE* orig, SAMPLE* ref0, SAMPLE* ref1, int s
   for (int i = 0; i < 6; i++) { cand_io[2 * i] = list[i].x; cand_io[2 * i + 1] = list[i].y; }
   mv_io[4] = mv.x; mv_io[5] = mv.y;
   return r;
+}
+
+/* ---- CDEF at frame level (tests/golden/gen_kat10.py -> kat10.npz).  Frames are packed planar 4:2:0 (Y, U, V, stride = width); mode: one byte per 4x4 cell,
+ * (height / 4) rows of (width / 4), the block_mode_t of deblock_data_t.  The frames are rebuilt with create_yuv_frame (pad 0, as mainenc.c:176-178 makes
+ * orig and rec), so rows have the alignment the reference's SIMD loads expect. */
+typedef struct {
+  enc_params params;
+  encoder_info_t ei;
+  yuv_frame_t rec, org;
+  stream_t stream;
+  uint8_t* sbuf;
+  int nfb;
+} cdef_shim_t;
+static void cdef_shim_planes(yuv_frame_t* f, SAMPLE* yuv, int to_frame) {
+  const int w = f->width, h = f->height;
+  SAMPLE* pl[3] = {f->y, f->u, f->v};
+  SAMPLE* p = yuv;
+  for (int k = 0; k < 3; k++) {
+    const int pw = k ? w / 2 : w, ph = k ? h / 2 : h, st = k ? f->stride_c : f->stride_y;
+    for (int i = 0; i < ph; i++, p += pw) {
+      if (to_frame) memcpy(pl[k] + i * st, p, pw * sizeof(SAMPLE));
+      else memcpy(p, pl[k] + i * st, pw * sizeof(SAMPLE));
+    }
+  }
+}
+static void cdef_shim_open(cdef_shim_t* c, SAMPLE* rec_yuv, SAMPLE* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, int qp, int cdef_bits, int speed) {
+  memset(c, 0, sizeof *c);
+  c->params.bitdepth = c->params.input_bitdepth = bitdepth; c->params.subsample = 420; c->params.cdef = speed + 1;
+  c->params.width = width; c->params.height = height;
+  c->ei.params = &c->params; c->ei.width = width; c->ei.height = height;
+  c->ei.frame_info.qp = qp; c->ei.frame_info.lambda = 1.0;
+  c->ei.cdef_damping = 5; c->ei.cdef_bits = cdef_bits;                                   /* encode_frame.c:685-686 */
+  TEMPLATE(create_yuv_frame)(&c->rec, width, height, 420, 0, 0, bitdepth, bitdepth);
+  TEMPLATE(create_yuv_frame)(&c->org, width, height, 420, 0, 0, bitdepth, bitdepth);
+  cdef_shim_planes(&c->rec, rec_yuv, 1); cdef_shim_planes(&c->org, org_yuv, 1);
+  c->ei.rec = &c->rec; c->ei.orig = &c->org;
+  const int ncell = (width / MIN_PB_SIZE) * (height / MIN_PB_SIZE);
+  c->ei.deblock_data = (deblock_data_t*)calloc(ncell, sizeof(deblock_data_t));
+  for (int i = 0; i < ncell; i++) c->ei.deblock_data[i].mode = (block_mode_t)mode[i];
+  c->nfb = ((width + 63) >> 6) * ((height + 63) >> 6);
+  c->ei.cdef = (cdef_strengths*)calloc(c->nfb, sizeof(cdef_strengths));
+  c->sbuf = (uint8_t*)calloc(1, 1 << 16);
+  c->stream.bytesize = 1 << 16; c->stream.bytepos = 0; c->stream.bitstream = c->sbuf; c->stream.bitbuf = 0; c->stream.bitrest = 32;
+  c->ei.stream = &c->stream;
+  use_simd = 1;
+}
+static void cdef_shim_close(cdef_shim_t* c) {
+  TEMPLATE(close_yuv_frame)(&c->rec); TEMPLATE(close_yuv_frame)(&c->org);
+  free(c->ei.deblock_data); free(c->ei.cdef); free(c->sbuf);
+}
+/* cdef_search + cdef_frame for planes 0, 1, 2 as encode_frame.c:768-774 runs them.  rec_yuv: the deblocked frame on entry, the filtered frame on return.
+ * Returns cdef_search's bits.  strengths / uv_strengths: 8 entries each (127 where the search wrote none, :688-689).  fb_sel[4 * fb ..]: level and
+ * sec_strength of plane[0], then of plane[1], of encoder_info->cdef[fb].  dir / var: per 8x8 luma block in frame raster order (width / 8 per row), -1 / 0 in
+ * all-skip filter blocks; what cdef_frame(plane 0) left, which the chroma planes then read.  bit_pos: length of the per-filter-block preset string. */
+int SHIM(ref_cdef_frame)(SAMPLE* rec_yuv, SAMPLE* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, int qp, int cdef_bits, int speed,
+                         int* strengths, int* uv_strengths, int* fb_sel, int* dir, int* var, int* bit_pos) {
+  cdef_shim_t c;
+  cdef_shim_open(&c, rec_yuv, org_yuv, mode, width, height, bitdepth, qp, cdef_bits, speed);
+  encoder_info_t* ei = &c.ei;
+  for (int i = 0; i < 8; i++) ei->cdef_strengths[i] = ei->cdef_uv_strengths[i] = 127;
+  for (int fb = 0; fb < c.nfb; fb++)
+    for (int k = 0; k < 64; k++) ei->cdef[fb].dir[k] = -1;
+  int bits = TEMPLATE(cdef_search)(ei->rec, ei->orig, ei->deblock_data, &ei->frame_info, ei, ei->cdef_strengths, ei->cdef_uv_strengths, ei->params->cdef - 1);
+  TEMPLATE(cdef_frame)(ei->cdef, ei->rec, ei->orig, ei->deblock_data, &c.stream, 0, ei->params->bitdepth, 0);
+  TEMPLATE(cdef_frame)(ei->cdef, ei->rec, ei->orig, ei->deblock_data, &c.stream, 0, ei->params->bitdepth, 1);
+  TEMPLATE(cdef_frame)(ei->cdef, ei->rec, ei->orig, ei->deblock_data, &c.stream, 0, ei->params->bitdepth, 2);
+  cdef_shim_planes(&c.rec, rec_yuv, 0);
+  for (int i = 0; i < 8; i++) { strengths[i] = ei->cdef_strengths[i]; uv_strengths[i] = ei->cdef_uv_strengths[i]; }
+  const int nfb_h = (width + 63) >> 6, bw = width / 8, bh = height / 8;
+  for (int fb = 0; fb < c.nfb; fb++)
+    for (int pl = 0; pl < 2; pl++) { fb_sel[4 * fb + 2 * pl] = ei->cdef[fb].plane[pl].level; fb_sel[4 * fb + 2 * pl + 1] = ei->cdef[fb].plane[pl].sec_strength; }
+  for (int by = 0; by < bh; by++)
+    for (int bx = 0; bx < bw; bx++) {
+      const cdef_strengths* s = &ei->cdef[(by >> 3) * nfb_h + (bx >> 3)];
+      dir[by * bw + bx] = s->dir[(by & 7) * 8 + (bx & 7)]; var[by * bw + bx] = s->dir[(by & 7) * 8 + (bx & 7)] < 0 ? 0 : s->var[(by & 7) * 8 + (bx & 7)];
+    }
+  *bit_pos = get_bit_pos(&c.stream);
+  cdef_shim_close(&c);
+  return bits;
+}
+/* The per-strength distortions cdef_search keeps in locals: its own loop (encode_frame.c:287-388) with its own functions - cdef_allskip, cdef_prepare_input,
+ * cdef_find_dir[_simd], adjust_strength, cdef_filter_block[_simd], dist_8x8 - and nothing else.  mse[(g * nfb + fb) * 64 + gi], g = 0 luma / 1 chroma, fb in
+ * frame raster order (zero for all-skip filter blocks and for gi >= the speed's number of strengths).  The generator checks the arrays against what
+ * cdef_search itself chose. */
+void SHIM(ref_cdef_mse)(SAMPLE* rec_yuv, SAMPLE* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, int speed, uint64_t* mse) {
+  cdef_shim_t c;
+  cdef_shim_open(&c, rec_yuv, org_yuv, mode, width, height, bitdepth, 32, 3, speed);
+  yuv_frame_t *rec = &c.rec, *org = &c.org;
+  deblock_data_t* deblock_data = c.ei.deblock_data;
+  const int num_fb_hor = (width + 63) >> 6, num_fb_ver = (height + 63) >> 6, nfb = c.nfb;
+  const int pri_damping = c.ei.cdef_damping, sec_damping = pri_damping, total_strengths = pristrengths[speed], bs = 8, bslog = 3, coeff_shift = bitdepth - 8;
+  const int padding = 2 + CDEF_FULL, hpadding = 16 - padding, stride16 = (64 + 2 * padding + 15) & ~15, offset16 = padding * stride16 + padding + hpadding;
+  uint16_t* src16 = thor_alloc((64 + 2 * padding) * stride16 * sizeof(uint16_t) + hpadding, 32);
+  SAMPLE* dst = thor_alloc(bs * bs * sizeof(SAMPLE), 32);
+  int cdef_directions_copy[8][2 + CDEF_FULL];
+  cdef_init(stride16, cdef_directions_copy);
+  memset(mse, 0, sizeof(uint64_t) * 2 * nfb * 64);
+  for (int k = 0; k < num_fb_ver; k++)
+    for (int l = 0; l < num_fb_hor; l++) {
+      const int xoff = l << 6, yoff = k << 6, ci = k * num_fb_hor + l;
+      if (cdef_allskip(xoff, yoff, width, height, deblock_data, 6)) continue;
+      int h = min(height, (k + 1) << 6) & 63, w = min(width, (l + 1) << 6) & 63;
+      h += !h << 6; w += !w << 6;
+      for (int plane = 0; plane < 3; plane++) {
+        const int sub = plane != 0 && rec->sub;
+        const int sstride = plane != 0 ? rec->stride_c : rec->stride_y;
+        SAMPLE* src_buffer = plane != 0 ? (plane == 1 ? rec->u : rec->v) : rec->y;
+        int sizex = min(width - xoff, 64) >> sub, sizey = min(height - yoff, 64) >> sub, xpos = xoff >> sub, ypos = yoff >> sub;
+        boundary_type bt = (TILE_LEFT_BOUNDARY & -!xpos) | (TILE_ABOVE_BOUNDARY & -!ypos) | (TILE_RIGHT_BOUNDARY & -(xpos == (width >> sub) - sizex)) |
+                           (TILE_BOTTOM_BOUNDARY & -(ypos == (height >> sub) - sizey));
+        TEMPLATE(cdef_prepare_input)(sizex, sizey, xpos, ypos, bt, padding, src16 + offset16, stride16, src_buffer, sstride);
+        for (int gi = 0; gi < total_strengths; gi++) {
+          const int pri_strength = priconv[speed][gi / CDEF_SEC_STRENGTHS], sec_strength = gi % CDEF_SEC_STRENGTHS;
+          uint64_t* acc = &mse[((size_t)(!!plane) * nfb + ci) * 64 + gi];
+          for (int m = 0; m < ((h + bs - 1) >> (bslog + sub)); m++)
+            for (int n = 0; n < ((w + bs - 1) >> (bslog + sub)); n++) {
+              xpos = (xoff >> sub) + n * bs; ypos = (yoff >> sub) + m * bs;
+              sizex = min((width >> sub) - xpos, bs); sizey = min((height >> sub) - ypos, bs);
+              const int index = ((yoff + m * 8) / MIN_PB_SIZE) * (width / MIN_PB_SIZE) + ((xoff + n * 8) / MIN_PB_SIZE);
+              if (plane == 0 && gi == 0)
+                c.ei.cdef[ci].dir[m * bs + n] = (use_simd ? TEMPLATE(cdef_find_dir_simd) : TEMPLATE(cdef_find_dir))(src_buffer + ypos * sstride + xpos, sstride, &c.ei.cdef[ci].var[m * bs + n], coeff_shift);
+              if (deblock_data[index].mode == MODE_SKIP) continue;
+              const int adj_str = plane ? pri_strength : adjust_strength(pri_strength, c.ei.cdef[ci].var[m * bs + n]);
+              const int adj_pri_damping = adj_str ? max(log2i(adj_str), pri_damping - !!plane) : pri_damping - !!plane;
+              const int adj_sec_damping = sec_damping - !!plane;
+#ifdef HBD
+              (use_simd ? cdef_filter_block_simd : cdef_filter_block)(NULL, dst, sizex, src16 + offset16 + n * bs + m * bs * stride16, stride16,
+#else
+              (use_simd ? cdef_filter_block_simd : cdef_filter_block)(dst, NULL, sizex, src16 + offset16 + n * bs + m * bs * stride16, stride16,
+#endif
+                  adj_str << coeff_shift, sec_strength << coeff_shift, pri_strength ? c.ei.cdef[ci].dir[m * bs + n] : 0, adj_pri_damping + coeff_shift,
+                  adj_sec_damping + coeff_shift, sizex, cdef_directions_copy, coeff_shift);
+              SAMPLE* org_buffer = (plane != 0 ? (plane == 1 ? org->u : org->v) : org->y) + ypos * sstride + xpos;
+              if (plane || sizex != 8 || sizey != 8) {
+                for (int i = 0; i < sizey; i++)
+                  for (int j = 0; j < sizex; j++)
+                    *acc += (dst[i * sizex + j] - org_buffer[i * sstride + j]) * (dst[i * sizex + j] - org_buffer[i * sstride + j]);
+              } else *acc += dist_8x8(dst, sizex, org_buffer, sstride, coeff_shift);
+            }
+        }
+      }
+    }
+  thor_free(src16); thor_free(dst);
+  cdef_shim_close(&c);
 }
 
 #ifndef REFSHIM_HBD

@@ -502,6 +502,24 @@ def kat_cdef_filter(plane, bsize, par, bitdepth=8):
     return out
 
 
+def kat_cdef_frame(rec, org, mode, width, height, qp, speed, cdef_bits, bitdepth=8):
+    """thor_hip_kat_cdef_frame: rec / org (S, width * height * 3 / 2) packed planar frames, mode (S, height / 4, width / 4) bytes, qp / speed / cdef_bits (S,).  Returns a dict of per-job arrays:
+    dir, var (S, h/8, w/8), fb_compact, fb_sel (S, nfb), mse (S, 2, nfb, 64), nb_bits, sb_count (S,), strengths, uv_strengths (S, 8), out (S, frame)."""
+    T = _pix(bitdepth)
+    rec = np.ascontiguousarray(rec, dtype=T); org = np.ascontiguousarray(org, dtype=T); mode = np.ascontiguousarray(mode, dtype=np.uint8)
+    S = len(rec)
+    nfb = ((width + 63) // 64) * ((height + 63) // 64)
+    qp, speed, cdef_bits = (np.ascontiguousarray(a, dtype=np.int32) for a in (qp, speed, cdef_bits))
+    assert rec.shape == org.shape == (S, width * height * 3 // 2) and mode.shape == (S, height // 4, width // 4) and len(qp) == len(speed) == len(cdef_bits) == S
+    d = np.zeros((S, height // 8, width // 8), dtype=np.int8); v = np.zeros((S, height // 8, width // 8), dtype=np.int32)
+    fbc = np.zeros((S, nfb), dtype=np.int32); fbs = np.zeros((S, nfb), dtype=np.int32)
+    mse = np.zeros((S, 2, nfb, 64), dtype=np.uint64); res = np.zeros((S, 34), dtype=np.int32)
+    out = np.zeros_like(rec)
+    _kat('thor_hip_kat_cdef_frame', S, _vp(rec), _vp(org), _vp(mode), width, height, bitdepth, _vp(qp), _vp(speed), _vp(cdef_bits), _vp(d), _vp(v), _vp(fbc), _vp(mse), _vp(res), _vp(fbs),
+         _vp(out))
+    return dict(dir=d, var=v, fb_compact=fbc, fb_sel=fbs, mse=mse, nb_bits=res[:, 0], strengths=res[:, 1:9], uv_strengths=res[:, 9:17], sb_count=res[:, 17], out=out)
+
+
 def kat_clpf(rec, org, width, height, qp, cells, strength, fb_log2, fb_on, bitdepth=8):
     T = _pix(bitdepth)
     rec = np.ascontiguousarray(rec, dtype=T); org = np.ascontiguousarray(org, dtype=T)

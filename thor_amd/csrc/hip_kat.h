@@ -420,6 +420,59 @@ int kat_clpf(const PIX* rec_yuv, const PIX* org_yuv, int width, int height, int 
   rec.release(); src.release(); org.release();
   return 0;
 }
+// The CDEF strength search and frame filter of `S` frames of one size through the product's launch sequence: CdefJobs filled as Engine::finish_frames fills
+// them (qp, speed and the cdef_bits guess per job), one backend::run_cdef call (copy + the five passes), everything the passes left behind copied back.
+template <typename PIX>
+int kat_cdef_frame(int S, const PIX* rec_yuv, const PIX* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, const int* qp, const int* speed, const int* cdef_bits,
+                   int8_t* dir, int* var, int* fb_compact, unsigned long long* mse, int* res, int* fb_sel, PIX* out_yuv) {
+  if (!rec_yuv || !org_yuv || !mode || !qp || !speed || !cdef_bits || !dir || !var || !fb_compact || !mse || !res || !fb_sel || !out_yuv) return 1;
+  if (S <= 0 || S > 64 || width < 8 || height < 8 || width % 8 || height % 8 || width > 8192 || height > 8192) return 1;
+  for (int s = 0; s < S; s++)
+    if (speed[s] < 0 || speed[s] > 2 || cdef_bits[s] < 0 || cdef_bits[s] > 3 || qp[s] < 0 || qp[s] > 51) return 1;
+  if (!ensure_init_any()) return 3;
+  static_assert(sizeof(CdefResult) % sizeof(int) == 0, "CdefResult is returned as ints");
+  const int nfb_h = (width + 63) / 64, nfb_v = (height + 63) / 64, nfb = nfb_h * nfb_v, nb8 = (width / 8) * (height / 8);
+  const size_t fsz = (size_t)width * height * 3 / 2, ncell = (size_t)(width / 4) * (height / 4);
+  std::vector<DevFrame<PIX>> rec(S), src(S), org(S);
+  std::vector<DbCell> cells(ncell * S);
+  memset(cells.data(), 0, cells.size() * sizeof(DbCell));
+  for (size_t i = 0; i < cells.size(); i++) { cells[i].mode = mode[i]; cells[i].size = 8; }
+  DevBuf<DbCell> d_cells(cells.size(), cells.data());
+  DevBuf<int8_t> d_dir((size_t)nb8 * S);
+  DevBuf<int> d_var((size_t)nb8 * S), d_fbc((size_t)nfb * S), d_sel((size_t)nfb * S), d_fbsel((size_t)nfb * S);
+  DevBuf<unsigned long long> d_mse((size_t)2 * nfb * kCdefMaxStr * S), d_tot(((size_t)kCdefMaxStr * kCdefMaxStr + nfb) * S);
+  DevBuf<CdefResult> d_res(S);
+  backend::dev_memset(d_dir, 0, (size_t)nb8 * S); backend::dev_memset(d_var, 0, (size_t)nb8 * S * sizeof(int));
+  backend::dev_memset(d_sel, 0, (size_t)nfb * S * sizeof(int)); backend::dev_memset(d_res, 0, sizeof(CdefResult) * S);
+  std::vector<CdefJob<PIX>> J(S);
+  for (int s = 0; s < S; s++) {
+    rec[s].alloc(width, height, 0); src[s].alloc(width, height, 0); org[s].alloc(width, height, 0);
+    upload_yuv(rec[s], rec_yuv + fsz * s, width, height); upload_yuv(org[s], org_yuv + fsz * s, width, height);
+    CdefJob<PIX>& C = J[s];
+    memset(&C, 0, sizeof(C));
+    C.rec = rec[s].p; C.src = src[s].p; C.org = org[s].p;
+    C.width = width; C.height = height; C.bitdepth = bitdepth;
+    C.cells = d_cells + ncell * s; C.cs = width / 4; C.nfb_h = nfb_h; C.nfb_v = nfb_v;
+    C.speed = speed[s]; C.damping = 5; C.cdef_bits = cdef_bits[s]; C.qp = qp[s];
+    C.dir = d_dir + (size_t)nb8 * s; C.var = d_var + (size_t)nb8 * s; C.fb_compact = d_fbc + (size_t)nfb * s;
+    C.mse = d_mse + (size_t)2 * nfb * kCdefMaxStr * s; C.sel = d_sel + (size_t)nfb * s; C.fb_sel = d_fbsel + (size_t)nfb * s;
+    C.res = d_res + s; C.tot = d_tot + ((size_t)kCdefMaxStr * kCdefMaxStr + nfb) * s;
+  }
+  {
+    DevBuf<CdefJob<PIX>> d_jobs(S, J.data());
+    backend::run_cdef<PIX>(d_jobs, J.data(), S);
+    HIPCHECK(hipGetLastError());
+    backend::dev_sync();
+  }
+  backend::d2h(dir, d_dir, (size_t)nb8 * S); backend::d2h(var, d_var, (size_t)nb8 * S * sizeof(int));
+  backend::d2h(fb_compact, d_fbc, (size_t)nfb * S * sizeof(int)); backend::d2h(fb_sel, d_fbsel, (size_t)nfb * S * sizeof(int));
+  backend::d2h(mse, d_mse, (size_t)2 * nfb * kCdefMaxStr * S * 8); backend::d2h(res, d_res, sizeof(CdefResult) * S);
+  for (int s = 0; s < S; s++) {
+    download_yuv(rec[s], out_yuv + fsz * s, width, height);
+    rec[s].release(); src[s].release(); org[s].release();
+  }
+  return 0;
+}
 // interpolate_frames(new, ref0, ref1, 2, 1) (common/temporal_interp.c:909) through the engine's own path (Engine::make_interp_frames, tk_interp_dev.h)
 template <typename PIX> int kat_interpolate(const PIX* yuv0, const PIX* yuv1, int width, int height, int bitdepth, PIX* out_yuv) {
   if (!yuv0 || !yuv1 || !out_yuv || width % 8 || height % 8 || width < 64 || height < 64) return 1;
@@ -541,6 +594,13 @@ extern "C" int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int w
                                  const int* strength, int fb_log2, const uint8_t* fb_on, uint32_t* stats, void* out_yuv) {
   KAT_BD(kat_clpf<uint8_t>((const uint8_t*)rec_yuv, (const uint8_t*)org_yuv, width, height, 8, qp, cells, strength, fb_log2, fb_on, stats, (uint8_t*)out_yuv),
          kat_clpf<uint16_t>((const uint16_t*)rec_yuv, (const uint16_t*)org_yuv, width, height, bitdepth, qp, cells, strength, fb_log2, fb_on, stats, (uint16_t*)out_yuv));
+}
+extern "C" int thor_hip_kat_cdef_frame(int n_jobs, const void* rec_yuv, const void* org_yuv, const uint8_t* mode, int width, int height, int bitdepth, const int* qp,
+                                       const int* speed, const int* cdef_bits, int8_t* dir, int* var, int* fb_compact, unsigned long long* mse, int* result, int* fb_sel, void* out_yuv) {
+  KAT_BD(kat_cdef_frame<uint8_t>(n_jobs, (const uint8_t*)rec_yuv, (const uint8_t*)org_yuv, mode, width, height, 8, qp, speed, cdef_bits, dir, var, fb_compact, mse, result, fb_sel,
+                                 (uint8_t*)out_yuv),
+         kat_cdef_frame<uint16_t>(n_jobs, (const uint16_t*)rec_yuv, (const uint16_t*)org_yuv, mode, width, height, bitdepth, qp, speed, cdef_bits, dir, var, fb_compact, mse, result,
+                                  fb_sel, (uint16_t*)out_yuv));
 }
 extern "C" int thor_hip_kat_motion_estimate(const void* cur, const void* ref, int width, int height, int bitdepth, int n, const int* par, const double* lambda,
                                             const int16_t* cand, int ncand_total, int* out) {

@@ -284,7 +284,10 @@ template <typename PIX> TK_DEV void cdef_pass_mse(const CdefJob<PIX>& J, int gid
 //           arithmetic exactly as before; chroma: sum e^2.  One atomic add per strength.
 // Integer results identical to the plain form by construction (no (int16_t) wrap can occur: |sum| <= 12 * 240 + 12 * 48, samples < 4096);
 // tests/hostsim/unit_cdef.cpp compares the two on random frames (edges, skipped blocks, partial filter blocks, 8/10/12 bits, the three speeds), and the
-// host simulation runs THIS form (lanes as a loop), so every golden stream with cdef on checks it.
+// host simulation runs THIS form (lanes as a loop), so every golden stream with cdef on checks it (-cdef 1 / 3: tests/golden/streams_cdef.json).  Against the
+// reference itself: tests/golden/kat10.npz holds the mse[] of cdef_search's own loop (and what the search and cdef_frame made of them) at the three speeds -
+// tests/test_kat_host_cdef.py runs this form on the CPU, tests/test_gpu_cdef.py the device code (dot-product builtins, kRow, four wavefronts per workgroup)
+// through k_cdef_mse as the encoder launches it.
 template <typename PIX> struct CdefWaveWs {
   enum { kRow = 64 * (int)sizeof(PIX) / 4 + 1 };   // dwords per strength row: 64 samples + one pad dword (lane = strength reads stride kRow: conflict-free)
   int16_t tile[12 * 12];
