@@ -174,6 +174,67 @@ int thor_hip_stage_frame_layout(thor_hip_encoder* e, int stream, int slot, const
 /* thor_hip_get_recon into a frame in `layout`, in host memory or (on_device != 0) in device memory.  Same return values. */
 int thor_hip_get_recon_layout(thor_hip_encoder* e, int stream, void* frame, const thor_hip_frame_layout* layout, int on_device);
 
+/* RGB frames, as screen capture, renderers and tensor pipelines hold them.  The format is given per call.  Staging an RGB frame means exactly:
+ * convert it to a planar 4:2:0 frame of input_bitdepth samples (below) and stage that frame (so every sample is then widened by
+ * bitdepth - input_bitdepth like any staged frame); fetching means: take thor_hip_get_recon's frame (already rounded back to input_bitdepth) and
+ * convert it to RGB (below).  One kernel each way (k_rgb_in, k_rgb_out); integers only.
+ *
+ * Samples: one byte for depth 8, a little-endian 16-bit word for depth 10 / 12 / 16.  A sample's value is s >> (16 - depth) when msb_aligned,
+ * else s (not masked: a value above 2^depth - 1 only meets the clamps below).  Packed orders hold 4 or 3 samples per pixel in the order named; the
+ * fourth channel (A) is ignored on input and written as 2^depth - 1 (shifted like the others when msb_aligned).  PLANAR_RGB is three planes R, G, B,
+ * plane_stride bytes apart, each with `pitch`.
+ *
+ * Constants, with n = input_bitdepth, M = 2^depth - 1, and Kr / Kb over 10000: 2990 / 1140 (BT.601), 2126 / 722 (BT.709), 2627 / 593 (BT.2020,
+ * non-constant luminance); Kg = 10000 - Kr - Kb (5870, 7152, 6780).
+ *   limited range: SY = 219 << (n - 8), SC = 224 << (n - 8), OY = 16 << (n - 8);  full range: SY = SC = 2^n - 1, OY = 0;  OC = 1 << (n - 1)
+ *   rdiv(a, b) = (2 * a + b) / (2 * b) in integers (a / b rounded to nearest, halves up; a, b positive; 64-bit)
+ * RGB -> Y'CbCr, F = 24 fractional bits:
+ *   yr = rdiv((Kr * SY) << F, 10000 * M)   yb = rdiv((Kb * SY) << F, 10000 * M)   yg = rdiv(SY << F, M) - yr - yb
+ *   ub = rdiv(SC << F, 2 * M)   ur = -rdiv((Kr * SC) << F, 2 * (10000 - Kb) * M)   ug = -ub - ur
+ *   vr = rdiv(SC << F, 2 * M)   vb = -rdiv((Kb * SC) << F, 2 * (10000 - Kr) * M)   vg = -vr - vb
+ *   Y(x, y)  = clamp((yr * R + yg * G + yb * B + (OY << F) + (1 << (F - 1))) >> F, 0, 2^n - 1)            for every pixel
+ *   chroma sample (i, j) sums taps of weight w, total 2^L, over the rows 2j and 2j + 1:
+ *     chroma_site 0 (centre): columns 2i, 2i + 1, w = 1, L = 2
+ *     chroma_site 1 (left):   columns 2i - 1, 2i, 2i + 1 with w = 1, 2, 1; column -1 is column 0; L = 3
+ *     tR = sum of w * R over the taps, tG and tB likewise
+ *   Cb(i, j) = clamp((ur * tR + ug * tG + ub * tB + (OC << (F + L)) + (1 << (F + L - 1))) >> (F + L), 0, 2^n - 1),  Cr with vr, vg, vb
+ *   (>> is the arithmetic shift: floor).  ur + ug + ub = vr + vg + vb = 0, so R = G = B gives Cb = Cr = OC; black gives Y = OY and white OY + SY.
+ *   The coefficients are at most 1.5 units of 2^-24 off, times M <= 65535: under 0.01 of a code value, so a result differs from the textbook
+ *   formula in float64, rounded to nearest, only where that lies within 0.01 of a rounding step, and then by one.
+ * Y'CbCr -> RGB, G = 20 fractional bits, chroma sample (i, j) used for the four pixels of its quad with either chroma_site:
+ *   iy = rdiv(M << G, SY)   rv = rdiv((2 * (10000 - Kr) * M) << G, 10000 * SC)   bu = rdiv((2 * (10000 - Kb) * M) << G, 10000 * SC)
+ *   gu = -rdiv((2 * Kb * (10000 - Kb) * M) << G, 10000 * Kg * SC)   gv = -rdiv((2 * Kr * (10000 - Kr) * M) << G, 10000 * Kg * SC)
+ *   l = iy * (Y - OY) + (1 << (G - 1))
+ *   R = clamp((l + rv * (Cr - OC)) >> G, 0, M)   G = clamp((l + gu * (Cb - OC) + gv * (Cr - OC)) >> G, 0, M)   B = clamp((l + bu * (Cb - OC)) >> G, 0, M)
+ *   written as value << (16 - depth) when msb_aligned.
+ * Bytes of a row beyond the picture's width and bytes between planes are never read on staging and never written on fetching. */
+enum { THOR_HIP_RGB_RGBA = 0, THOR_HIP_RGB_BGRA = 1, THOR_HIP_RGB_ARGB = 2, THOR_HIP_RGB_ABGR = 3, THOR_HIP_RGB_RGB = 4, THOR_HIP_RGB_BGR = 5,
+       THOR_HIP_RGB_PLANAR_RGB = 6 };
+enum { THOR_HIP_MATRIX_BT601 = 0, THOR_HIP_MATRIX_BT709 = 1, THOR_HIP_MATRIX_BT2020 = 2 };
+typedef struct thor_hip_rgb_format {
+  int    size;         /* sizeof(thor_hip_rgb_format) */
+  int    order;        /* THOR_HIP_RGB_* */
+  int    depth;        /* bits per channel: 8 (one byte), 10, 12 or 16 (16-bit words) */
+  int    msb_aligned;  /* depth 10 / 12 only: the value sits in the high bits of the word, as in P010 */
+  int    matrix;       /* THOR_HIP_MATRIX_* */
+  int    full_range;   /* 0: 16..235 / 16..240 scaled to input_bitdepth; 1: 0..2^input_bitdepth - 1 */
+  int    chroma_site;  /* 0: centre of the 2x2 quad; 1: left (the MPEG-2 / H.264 default) */
+  int    pitch;        /* bytes between rows; 0 = tight */
+  size_t plane_stride; /* PLANAR_RGB only: bytes between planes; 0 = pitch * height */
+} thor_hip_rgb_format;
+/* Bytes a frame in `fmt` spans from its base; 0 if the format is refused: `size` is wrong; order, depth, matrix, full_range or chroma_site is
+ * unknown; msb_aligned is set with depth 8 or 16; the pitch is negative, below the row's bytes or no multiple of the sample size; plane_stride
+ * is set for a packed order, is below pitch * height or is no multiple of the sample size.  thor_hip_rgb_bytes_for needs no encoder and no device
+ * (width and height: multiples of 8, at least 16). */
+size_t thor_hip_rgb_bytes(const thor_hip_encoder* e, const thor_hip_rgb_format* fmt);
+size_t thor_hip_rgb_bytes_for(int width, int height, const thor_hip_rgb_format* fmt);
+/* thor_hip_stage_frame_layout / thor_hip_get_recon_layout for an RGB frame: same return values (0; 1 for a bad argument, a refused format or a base
+ * pointer that is not sample-aligned - found before the device is touched), same ordering, synchronous at return on the library's stream.  A host
+ * frame is copied once into the device buffer the encoder keeps for layouts; a device frame is read (written) in place.  Rows that are 16-byte
+ * aligned (4-byte aligned for RGB / BGR) move in whole vectors, anything else sample by sample. */
+int thor_hip_stage_frame_rgb(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_rgb_format* fmt, int on_device);
+int thor_hip_get_recon_rgb(thor_hip_encoder* e, int stream, void* frame, const thor_hip_rgb_format* fmt, int on_device);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -356,6 +417,11 @@ int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int h, int bit
  * Returns 0, 1 = bad argument or refused layout (before the device is touched), 3 = no device. */
 int thor_hip_kat_layout_in(const void* src, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* planar_out);
 int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* dst);
+/* The same for k_rgb_in / k_rgb_out: `src` / `dst` hold thor_hip_rgb_bytes_for(w, h, fmt) bytes in `fmt` (dst: plus 64 guard bytes, all of it uploaded
+ * before the kernel runs and downloaded afterwards); the planar frames are at `bitdepth` (k_rgb_out rounds back to input_bitdepth first).  Any depth
+ * of `fmt` goes with any input_bitdepth <= bitdepth.  Same return values. */
+int thor_hip_kat_rgb_in(const void* src, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, void* planar_out);
+int thor_hip_kat_rgb_out(const void* planar_in, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, void* dst);
 
 /* Resources of the persistent superblock kernel (sample_bytes 1: 8-bit kernel, 2: 16-bit kernel, 0: the 8-bit kernel's second build for runs of few
  * streams - 256 registers, two workgroups per CU, chosen by the library when a run cannot fill more; THOR_HIP_KERNEL=std|lat|wide forces one; 3: its third build - eight wavefronts per workgroup, one workgroup per CU, for runs of very few streams) as the HIP runtime reports them: registers per lane,

@@ -100,6 +100,42 @@ class FrameLayout(C.Structure):
         return cls(CHROMA_UV, 1, pitch or 0, pitch or 0, offset_uv)
 
 
+RGB_RGBA, RGB_BGRA, RGB_ARGB, RGB_ABGR, RGB_RGB, RGB_BGR, RGB_PLANAR = range(7)   # THOR_HIP_RGB_*
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2                                # THOR_HIP_MATRIX_*
+
+
+class RgbFormat(C.Structure):
+    """thor_hip_rgb_format (include/thor_hip.h): an RGB frame - channel order, bits per channel (8: bytes; 10 / 12 / 16: 16-bit words), conversion
+    matrix, range, chroma siting, row pitch in bytes (0 = tight) and, for planar frames, the bytes between planes (0 = adjacent)."""
+    _fields_ = [('size', C.c_int), ('order', C.c_int), ('depth', C.c_int), ('msb_aligned', C.c_int), ('matrix', C.c_int), ('full_range', C.c_int),
+                ('chroma_site', C.c_int), ('pitch', C.c_int), ('plane_stride', C.c_size_t)]
+
+    def __init__(self, order=RGB_RGBA, depth=8, msb_aligned=0, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, plane_stride=0):
+        super().__init__(C.sizeof(RgbFormat), order, depth, msb_aligned, matrix, full_range, chroma_site, pitch, plane_stride)
+
+    @classmethod
+    def rgba(cls, depth=8, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, msb_aligned=0):
+        return cls(RGB_RGBA, depth, msb_aligned, matrix, full_range, chroma_site, pitch)
+
+    @classmethod
+    def bgra(cls, depth=8, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, msb_aligned=0):
+        return cls(RGB_BGRA, depth, msb_aligned, matrix, full_range, chroma_site, pitch)
+
+    @classmethod
+    def rgb24(cls, depth=8, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, msb_aligned=0):
+        """Three samples per pixel, R first (of 16-bit words when depth is above 8)."""
+        return cls(RGB_RGB, depth, msb_aligned, matrix, full_range, chroma_site, pitch)
+
+    @classmethod
+    def bgr24(cls, depth=8, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, msb_aligned=0):
+        return cls(RGB_BGR, depth, msb_aligned, matrix, full_range, chroma_site, pitch)
+
+    @classmethod
+    def planar(cls, depth=8, matrix=MATRIX_BT709, full_range=0, chroma_site=1, pitch=0, msb_aligned=0, plane_stride=0):
+        """Three planes R, G, B: a contiguous torch tensor of shape 3 x H x W."""
+        return cls(RGB_PLANAR, depth, msb_aligned, matrix, full_range, chroma_site, pitch, plane_stride)
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -149,6 +185,15 @@ def lib():
         L.thor_hip_get_recon_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, LP, C.c_int]
         L.thor_hip_kat_layout_in.argtypes = [C.c_void_p, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_kat_layout_out.argtypes = [C.c_void_p, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        RP = C.POINTER(RgbFormat)
+        L.thor_hip_rgb_bytes.restype = C.c_size_t
+        L.thor_hip_rgb_bytes.argtypes = [C.c_void_p, RP]
+        L.thor_hip_rgb_bytes_for.restype = C.c_size_t
+        L.thor_hip_rgb_bytes_for.argtypes = [C.c_int, C.c_int, RP]
+        L.thor_hip_stage_frame_rgb.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, RP, C.c_int]
+        L.thor_hip_get_recon_rgb.argtypes = [C.c_void_p, C.c_int, C.c_void_p, RP, C.c_int]
+        L.thor_hip_kat_rgb_in.argtypes = [C.c_void_p, RP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_kat_rgb_out.argtypes = [C.c_void_p, RP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -224,6 +269,41 @@ class Encoder:
         rc = lib().thor_hip_stage_frame_device(self.h, stream, slot, C.c_void_p(dev_ptr))
         if rc:
             raise RuntimeError(f'thor_hip_stage_frame_device rc={rc}')
+
+    def rgb_bytes(self, fmt):
+        """Bytes an RGB frame in `fmt` (an RgbFormat) spans; raises for a format the library refuses."""
+        n = lib().thor_hip_rgb_bytes(self.h, C.byref(fmt))
+        if not n:
+            raise ValueError('RGB format refused (unknown order / depth / matrix, msb_aligned with depth 8 or 16, pitch below the row ...)')
+        return n
+
+    def stage_rgb(self, stream, slot, array, fmt):
+        """Stage a host RGB frame (rgb_bytes(fmt) bytes in `fmt`): converted to 4:2:0 at input_bitdepth on the device, then staged."""
+        frame = np.ascontiguousarray(array).view(np.uint8).reshape(-1)
+        assert frame.size >= self.rgb_bytes(fmt)
+        rc = lib().thor_hip_stage_frame_rgb(self.h, stream, slot, frame.ctypes.data_as(C.c_void_p), C.byref(fmt), 0)
+        if rc:
+            raise RuntimeError(f'thor_hip_stage_frame_rgb rc={rc}')
+
+    def stage_rgb_device(self, stream, slot, dev_ptr, fmt):
+        """Stage an RGB frame that lives in HBM (e.g. tensor.data_ptr()), read in place by the kernel that writes the slot."""
+        rc = lib().thor_hip_stage_frame_rgb(self.h, stream, slot, C.c_void_p(dev_ptr), C.byref(fmt), 1)
+        if rc:
+            raise RuntimeError(f'thor_hip_stage_frame_rgb rc={rc}')
+
+    def recon_rgb(self, stream, fmt):
+        """Reconstruction of the stream's last coded frame as RGB: rgb_bytes(fmt) bytes (row padding and gaps between planes are zero)."""
+        out = np.zeros(self.rgb_bytes(fmt), dtype=np.uint8)
+        rc = lib().thor_hip_get_recon_rgb(self.h, stream, out.ctypes.data_as(C.c_void_p), C.byref(fmt), 0)
+        if rc:
+            raise RuntimeError(f'thor_hip_get_recon_rgb rc={rc}')
+        return out
+
+    def recon_rgb_device(self, stream, dev_ptr, fmt):
+        """The same into device memory (rgb_bytes(fmt) bytes at dev_ptr); only the picture's samples are written.  Synchronous at return."""
+        rc = lib().thor_hip_get_recon_rgb(self.h, stream, C.c_void_p(dev_ptr), C.byref(fmt), 1)
+        if rc:
+            raise RuntimeError(f'thor_hip_get_recon_rgb rc={rc}')
 
     def begin_sequence(self, stream, skip, num_frames, file_frames):
         """Fix the chunk [skip, skip+num_frames) of a file_frames-long input (thor_hip_begin_sequence)."""
@@ -674,4 +754,27 @@ def kat_layout_out(planar, layout, width, height, input_bitdepth, bitdepth, dst)
     a = _depth_frame(planar, bitdepth, width, height)
     assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.size == layout_bytes(layout, width, height, input_bitdepth) + 64 > 64
     _kat('thor_hip_kat_layout_out', _vp(a), C.byref(layout), width, height, input_bitdepth, bitdepth, _vp(dst))
+    return dst
+
+
+def rgb_bytes(fmt, width, height):
+    """thor_hip_rgb_bytes_for: bytes a width x height RGB frame in `fmt` spans, 0 if the format is refused.  Needs no encoder and no device."""
+    return lib().thor_hip_rgb_bytes_for(width, height, C.byref(fmt))
+
+
+def kat_rgb_in(src, fmt, width, height, input_bitdepth, bitdepth):
+    """thor_hip_kat_rgb_in: an RGB frame (a uint8 array of at least rgb_bytes; its address decides the kernel's path) through k_rgb_in -> packed
+    planar 4:2:0 at `bitdepth`."""
+    assert src.dtype == np.uint8 and src.flags.c_contiguous and src.size >= rgb_bytes(fmt, width, height) > 0
+    out = np.zeros(width * height * 3 // 2, dtype=_pix(bitdepth))
+    _kat('thor_hip_kat_rgb_in', _vp(src), C.byref(fmt), width, height, input_bitdepth, bitdepth, _vp(out))
+    return out
+
+
+def kat_rgb_out(planar, fmt, width, height, input_bitdepth, bitdepth, dst):
+    """thor_hip_kat_rgb_out: a packed planar 4:2:0 frame at `bitdepth` through k_rgb_out into `dst`, in place: a uint8 array of rgb_bytes + 64 guard
+    bytes, all of which travel to the device and back."""
+    a = _depth_frame(planar, bitdepth, width, height)
+    assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.size == rgb_bytes(fmt, width, height) + 64 > 64
+    _kat('thor_hip_kat_rgb_out', _vp(a), C.byref(fmt), width, height, input_bitdepth, bitdepth, _vp(dst))
     return dst

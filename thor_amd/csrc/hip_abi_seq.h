@@ -81,6 +81,12 @@ static bool layout_resolved(const thor_hip_frame_layout* l, int width, int heigh
   return resolve_layout(l->chroma, l->msb_aligned, l->pitch_y, l->pitch_c, l->offset_u, l->offset_v, width, height, input_bitdepth, L);
 }
 
+// The caller's RGB format against a width x height picture of input_bitdepth samples; false: refused (a wrong `size` included).  Touches no device.
+static bool rgb_resolved(const thor_hip_rgb_format* f, int width, int height, int input_bitdepth, RgbFormat& R) {
+  if (!f || f->size != (int)sizeof(thor_hip_rgb_format)) return false;
+  return resolve_rgb(f->order, f->depth, f->msb_aligned, f->matrix, f->full_range, f->chroma_site, f->pitch, f->plane_stride, width, height, input_bitdepth, R);
+}
+
 extern "C" {
 
 int thor_hip_params_from_config(thor_hip_params* p, const char* cfg_path) {
@@ -108,7 +114,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420") return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given) return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -357,6 +363,44 @@ int thor_hip_get_recon_layout(thor_hip_encoder* e, int stream, void* frame, cons
       HIPCHECK(hipStreamSynchronize(g_stream));
     } else
       E.eng.fetch_layout_host(E.eng.st[stream].rec.p, frame, L);
+  });
+  return 0;
+}
+
+// ---- RGB frames: tk_filters.h RgbFormat, k_rgb_in / k_rgb_out ----
+size_t thor_hip_rgb_bytes_for(int width, int height, const thor_hip_rgb_format* fmt) {
+  RgbFormat R;
+  return rgb_resolved(fmt, width, height, 8, R) ? R.bytes : 0;  // the size does not depend on the input depth
+}
+size_t thor_hip_rgb_bytes(const thor_hip_encoder* e, const thor_hip_rgb_format* fmt) {
+  return e ? thor_hip_rgb_bytes_for(e->sp.width, e->sp.height, fmt) : 0;
+}
+int thor_hip_stage_frame_rgb(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_rgb_format* fmt, int on_device) {
+  RgbFormat R;
+  if (!e || stream < 0 || stream >= e->S || slot < 0 || !frame) return 1;
+  if (!rgb_resolved(fmt, e->sp.width, e->sp.height, e->sp.input_bitdepth, R) || (uintptr_t)frame % R.sbytes) return 1;
+  ENC_DISPATCH(e, {
+    auto& v = E.staged[stream];
+    if ((int)v.size() <= slot) v.resize(slot + 1);
+    if (!v[slot].base_y) v[slot].alloc(e->sp.width, e->sp.height, 0);
+    if (on_device) {  // the kernel reads the caller's buffer and writes the slot
+      E.eng.rgb_in(frame, R, v[slot].p);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+    } else
+      E.eng.stage_rgb_host(frame, R, v[slot].p);
+  });
+  return 0;
+}
+int thor_hip_get_recon_rgb(thor_hip_encoder* e, int stream, void* frame, const thor_hip_rgb_format* fmt, int on_device) {
+  RgbFormat R;
+  if (!e || stream < 0 || stream >= e->S || !frame) return 1;
+  if (!rgb_resolved(fmt, e->sp.width, e->sp.height, e->sp.input_bitdepth, R) || (uintptr_t)frame % R.sbytes) return 1;
+  ENC_DISPATCH(e, {
+    if (on_device) {
+      E.eng.rgb_out(E.eng.st[stream].rec.p, frame, R);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+    } else
+      E.eng.fetch_rgb_host(E.eng.st[stream].rec.p, frame, R);
   });
   return 0;
 }

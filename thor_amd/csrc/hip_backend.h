@@ -370,6 +370,25 @@ template void launch_layout_in<uint16_t>(const void*, const PixLayout&, const Pl
 template void launch_layout_out<uint8_t>(const Plane3<uint8_t>&, void*, const PixLayout&, int, int, int, int);
 template void launch_layout_out<uint16_t>(const Plane3<uint16_t>&, void*, const PixLayout&, int, int, int, int);
 
+// An RGB frame <-> the engine's planes, on g_stream (tk_encoder.h declares them).  `frame`: device memory, R.bytes of it.  The 8-bit engine exists
+// only for bitdepth == input_bitdepth == 8; the RGB side has one or two bytes per sample with either engine.
+template <typename PIX> void launch_rgb_in(const void* frame, const RgbFormat& R, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth) {
+  const int up = bitdepth - input_bitdepth;
+  if (R.sbytes == 1) hipLaunchKernelGGL((k_rgb_in<uint8_t, PIX>), dim3(height / 2), dim3(256), 0, g_stream, frame, R, dst, width, height, up);
+  else hipLaunchKernelGGL((k_rgb_in<uint16_t, PIX>), dim3(height / 2), dim3(256), 0, g_stream, frame, R, dst, width, height, up);
+  HIPCHECK(hipGetLastError());
+}
+template <typename PIX> void launch_rgb_out(const Plane3<PIX>& src, void* frame, const RgbFormat& R, int width, int height, int bitdepth, int input_bitdepth) {
+  const int shift = bitdepth - input_bitdepth;
+  if (R.sbytes == 1) hipLaunchKernelGGL((k_rgb_out<PIX, uint8_t>), dim3(height / 2), dim3(256), 0, g_stream, src, frame, R, width, height, shift);
+  else hipLaunchKernelGGL((k_rgb_out<PIX, uint16_t>), dim3(height / 2), dim3(256), 0, g_stream, src, frame, R, width, height, shift);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_rgb_in<uint8_t>(const void*, const RgbFormat&, const Plane3<uint8_t>&, int, int, int, int);
+template void launch_rgb_in<uint16_t>(const void*, const RgbFormat&, const Plane3<uint16_t>&, int, int, int, int);
+template void launch_rgb_out<uint8_t>(const Plane3<uint8_t>&, void*, const RgbFormat&, int, int, int, int);
+template void launch_rgb_out<uint16_t>(const Plane3<uint16_t>&, void*, const RgbFormat&, int, int, int, int);
+
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {
 // Owning device array of n elements, zeroed (dev_alloc clears), filled from `h` when given; freed with its scope.

@@ -778,6 +778,50 @@ extern "C" int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_fra
   else kat_layout_out<uint16_t>((const uint16_t*)planar_in, L, w, h, input_bitdepth, bitdepth, dst);
   return 0;
 }
+// k_rgb_in / k_rgb_out on host buffers, like the two above: the device copy keeps the host pointer's offset from a 16-byte boundary.
+static int kat_rgb_args(const void* rgb, const void* planar, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, RgbFormat& R) {
+  auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };
+  if (!rgb || !planar || w % 8 || h % 8 || w < 16 || h < 16 || !ok(bitdepth) || !ok(input_bitdepth) || input_bitdepth > bitdepth) return 1;
+  return !rgb_resolved(fmt, w, h, input_bitdepth, R) || (uintptr_t)rgb % R.sbytes;
+}
+template <typename PIX> static void kat_rgb_in(const void* src, const RgbFormat& R, int w, int h, int input_bitdepth, int bitdepth, PIX* out) {
+  const size_t skew = (uintptr_t)src & 15;
+  DevBuf<uint8_t> d(R.bytes + 16);
+  backend::h2d(d.p + skew, src, R.bytes);
+  DevFrame<PIX> f;
+  f.alloc(w, h, 0);
+  launch_rgb_in<PIX>(d.p + skew, R, f.p, w, h, bitdepth, input_bitdepth);
+  backend::dev_sync();
+  download_yuv(f, out, w, h);
+  f.release();
+}
+template <typename PIX> static void kat_rgb_out(const PIX* in, const RgbFormat& R, int w, int h, int input_bitdepth, int bitdepth, void* dst) {
+  const size_t skew = (uintptr_t)dst & 15;
+  DevBuf<uint8_t> d(R.bytes + kKatLayoutGuard + 16);
+  backend::h2d(d.p + skew, dst, R.bytes + kKatLayoutGuard);
+  DevFrame<PIX> f;
+  f.alloc(w, h, 0);
+  upload_yuv(f, in, w, h);
+  launch_rgb_out<PIX>(f.p, d.p + skew, R, w, h, bitdepth, input_bitdepth);
+  backend::d2h(dst, d.p + skew, R.bytes + kKatLayoutGuard);
+  f.release();
+}
+extern "C" int thor_hip_kat_rgb_in(const void* src, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, void* planar_out) {
+  RgbFormat R;
+  if (kat_rgb_args(src, planar_out, fmt, w, h, input_bitdepth, bitdepth, R)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_rgb_in<uint8_t>(src, R, w, h, input_bitdepth, bitdepth, (uint8_t*)planar_out);
+  else kat_rgb_in<uint16_t>(src, R, w, h, input_bitdepth, bitdepth, (uint16_t*)planar_out);
+  return 0;
+}
+extern "C" int thor_hip_kat_rgb_out(const void* planar_in, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, void* dst) {
+  RgbFormat R;
+  if (kat_rgb_args(dst, planar_in, fmt, w, h, input_bitdepth, bitdepth, R)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_rgb_out<uint8_t>((const uint8_t*)planar_in, R, w, h, input_bitdepth, bitdepth, dst);
+  else kat_rgb_out<uint16_t>((const uint16_t*)planar_in, R, w, h, input_bitdepth, bitdepth, dst);
+  return 0;
+}
 extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
   KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),
          kat_interpolate<uint16_t>((const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, (uint16_t*)out_yuv));

@@ -218,4 +218,16 @@ __global__ __launch_bounds__(256) void k_layout_out(Plane3<PIX> src, void* frame
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
   layout_out_rows<PIX, DST>(src, frame, L, width, height, shift, input_bitdepth, (int)blockIdx.x * 4 + wave, (int)gridDim.x * 4, lane, 64);
 }
+
+// ---- RGB frames (tk_filters.h: rgb_in_rows, rgb_out_rows) --------
+// One frame per launch, one workgroup per pair of luma rows with its chroma row, its 256 lanes along the rows in runs of whole 16-byte vectors of the
+// RGB side.  `frame`: device memory in format R, whose coefficients come by value.  No LDS, no atomics.
+template <typename SRC, typename PIX>
+__global__ __launch_bounds__(256) void k_rgb_in(const void* frame, RgbFormat R, Plane3<PIX> dst, int width, int height, int up) {
+  rgb_in_rows<SRC, PIX>(frame, R, dst, width, height, up, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, 256);
+}
+template <typename PIX, typename DST>
+__global__ __launch_bounds__(256) void k_rgb_out(Plane3<PIX> src, void* frame, RgbFormat R, int width, int height, int shift) {
+  rgb_out_rows<PIX, DST>(src, frame, R, width, height, shift, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, 256);
+}
 }  // namespace tk

@@ -19,7 +19,12 @@ struct CliArgs {
   int num_frames = 600, skip = 0, streams = 1;
   int snrcalc = 1;           // -snrcalc (enc/strings.c:340): PSNR of every frame in the report
   std::string statfile;      // -stat FILE: one summary line per stream appended (enc/mainenc.c:652-667)
-  std::string pixfmt = "i420";  // -pixfmt i420|nv12|nv21|p010: layout of the -if and -rf files (tight rows; not an option of the reference)
+  std::string pixfmt = "i420";  // -pixfmt i420|nv12|nv21|p010|rgba|bgra|rgb24|bgr24: layout of the -if and -rf files (tight rows; not an option of the reference)
+  // RGB files (-pixfmt rgba|bgra|rgb24|bgr24; one byte per channel with 8-bit input, else 16-bit words with the value in the low bits):
+  int rgb_matrix = 1;        // -rgbmatrix 601|709|2020 -> 0, 1, 2
+  int rgb_full = 0;          // -rgbrange limited|full
+  int rgb_site = 1;          // -rgbsite centre|left
+  bool rgb_given = false;    // one of the three was given: front-end options like -pixfmt
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -40,6 +45,9 @@ static inline void cli_tokens_from_file(const std::string& path, std::vector<std
   }
 }
 
+// -pixfmt rgba|bgra|rgb24|bgr24 as an order of RgbFormat (resolve_rgb); -1: not an RGB format
+static inline int cli_rgb_order(const std::string& pixfmt) { return pixfmt == "rgba" ? 0 : pixfmt == "bgra" ? 1 : pixfmt == "rgb24" ? 4 : pixfmt == "bgr24" ? 5 : -1; }
+
 static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
   for (size_t i = 0; i + 1 < t.size(); i += 2) {
     const std::string& k = t[i];
@@ -58,7 +66,15 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
     else if (k == "-stat") a.statfile = v;
     else if (k == "-pixfmt") {
       a.pixfmt = v;
-      if (v != "i420" && v != "nv12" && v != "nv21" && v != "p010" && a.unsupported.empty()) a.unsupported = k + " " + v;
+      if (v != "i420" && v != "nv12" && v != "nv21" && v != "p010" && cli_rgb_order(v) < 0 && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
+    else if (k == "-rgbmatrix" || k == "-rgbrange" || k == "-rgbsite") {
+      a.rgb_given = true;
+      bool ok = true;
+      if (k == "-rgbmatrix") { a.rgb_matrix = v == "601" ? 0 : v == "709" ? 1 : 2; ok = v == "601" || v == "709" || v == "2020"; }
+      else if (k == "-rgbrange") { a.rgb_full = v == "full"; ok = v == "full" || v == "limited"; }
+      else { a.rgb_site = v == "left"; ok = v == "left" || v == "centre"; }
+      if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
     }
     else if (k == "-width") p.width = I();
     else if (k == "-height") p.height = I();
@@ -161,8 +177,14 @@ static inline bool cli_pixfmt_layout(const std::string& pixfmt, int width, int h
 template <typename PIX> int cli_run(const CliArgs& a) {
   const SeqParams& p = a.sp;
   PixLayout lay;
-  const bool use_layout = a.pixfmt != "i420";   // i420 is the path the files always took
-  if (!cli_pixfmt_layout(a.pixfmt, p.width, p.height, p.input_bitdepth, lay)) {
+  RgbFormat rgb;
+  const bool use_rgb = cli_rgb_order(a.pixfmt) >= 0;   // tight rows, a byte per channel with 8-bit input, else 16-bit words with the value in the low bits
+  if (use_rgb && !resolve_rgb(cli_rgb_order(a.pixfmt), p.input_bitdepth > 8 ? 16 : 8, 0, a.rgb_matrix, a.rgb_full, a.rgb_site, 0, 0, p.width, p.height, p.input_bitdepth, rgb)) {
+    fprintf(stderr, "Run-time error...\n-pixfmt %s cannot hold this picture\n...now exiting to system...\n", a.pixfmt.c_str());
+    return 2;
+  }
+  const bool use_layout = a.pixfmt != "i420" && !use_rgb;   // i420 is the path the files always took
+  if (!use_rgb && !cli_pixfmt_layout(a.pixfmt, p.width, p.height, p.input_bitdepth, lay)) {
     fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", a.pixfmt.c_str());
     return 2;
   }
@@ -171,7 +193,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   Engine<PIX> eng;
   eng.frame_distortion = a.snrcalc != 0;
   eng.open(p, a.streams);
-  const size_t fsz = eng.frame_bytes();  // the files hold input-depth samples (-if and -rf: common/common_frame.c:484-650)
+  const size_t fsz = use_rgb ? rgb.bytes : eng.frame_bytes();  // the files hold input-depth samples (-if and -rf: common/common_frame.c:484-650), or RGB frames
   std::vector<uint8_t> frame(fsz), rec(fsz);
   std::vector<FILE*> fr(a.streams, nullptr);
   auto name = [&](const std::string& base, int s) { return a.streams == 1 ? base : base + "." + std::to_string(s); };
@@ -182,8 +204,8 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   const int file_frames = (int)(ftell(fi) / (long)fsz);
   for (int s = 0; s < a.streams; s++) eng.begin_sequence(s, a.skip + s * a.num_frames, a.num_frames, file_frames);
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
-  auto upload = [&](int s) { if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
-  auto download = [&](int s) { if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
+  auto upload = [&](int s) { if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
+  auto download = [&](int s) { if (use_rgb) eng.fetch_rgb_host(eng.st[s].rec.p, rec.data(), rgb); else if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
   // THOR_STAGGER=1 (tests): the streams in two groups half a frame apart (Engine::encode_run) instead of lock step
   if (getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER")) && a.streams > 1) {
     int rc = 0;

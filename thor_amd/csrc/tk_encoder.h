@@ -73,6 +73,9 @@ void launch_frame_sse_depth(const FrameJob<uint16_t>* jobs, const FrameJob<uint1
 // library's stream.  `frame`: device memory.  The host build calls the row functions directly (Engine::layout_in / layout_out).
 template <typename PIX> void launch_layout_in(const void* frame, const PixLayout& L, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth);
 template <typename PIX> void launch_layout_out(const Plane3<PIX>& src, void* frame, const PixLayout& L, int width, int height, int bitdepth, int input_bitdepth);
+// An RGB frame (tk_filters.h: RgbFormat, rgb_in_rows, rgb_out_rows) <-> planes at the engine's depth, one launch each on the library's stream.
+template <typename PIX> void launch_rgb_in(const void* frame, const RgbFormat& R, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth);
+template <typename PIX> void launch_rgb_out(const Plane3<PIX>& src, void* frame, const RgbFormat& R, int width, int height, int bitdepth, int input_bitdepth);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -607,6 +610,41 @@ template <typename PIX> class Engine {
       memcpy(out + L.off_u + i * L.pitch_c, &tmp[L.off_u + i * L.pitch_c], row_c);
       if (L.chroma == 0) memcpy(out + L.off_v + i * L.pitch_c, &tmp[L.off_v + i * L.pitch_c], row_c);
     }
+  }
+
+  // An RGB frame (tk_filters.h: RgbFormat) in device memory -> planes at the engine's depth, and planes -> such a frame: colour conversion, 4:2:0
+  // downsampling and depth conversion in one kernel.  Asynchronous on the device.
+  void rgb_in(const void* frame, const RgbFormat& R, const Plane3<PIX>& dst) {
+#if TK_HOST
+    if (R.sbytes == 1) rgb_in_rows<uint8_t, PIX>(frame, R, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+    else rgb_in_rows<uint16_t, PIX>(frame, R, dst, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+#else
+    launch_rgb_in<PIX>(frame, R, dst, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+  }
+  void rgb_out(const Plane3<PIX>& src, void* frame, const RgbFormat& R) {
+#if TK_HOST
+    if (R.sbytes == 1) rgb_out_rows<PIX, uint8_t>(src, frame, R, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+    else rgb_out_rows<PIX, uint16_t>(src, frame, R, sp.width, sp.height, depth_shift(), 0, 1, 0, 1);
+#else
+    launch_rgb_out<PIX>(src, frame, R, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+  }
+  // The same for a frame in host memory, through the device buffer of the layouts (layout_buf).  Synchronous.
+  void stage_rgb_host(const void* frame, const RgbFormat& R, const Plane3<PIX>& dst) {
+    backend::h2d(layout_buf(R.bytes), frame, R.bytes);
+    rgb_in(d_layout, R, dst);
+    backend::dev_sync();
+  }
+  // Only the picture's bytes of `frame` are written, as in fetch_layout_host.
+  void fetch_rgb_host(const Plane3<PIX>& src, void* frame, const RgbFormat& R) {
+    rgb_out(src, layout_buf(R.bytes), R);
+    const size_t row = (size_t)sp.width * R.sbytes * (R.kind == 0 ? 4 : R.kind == 1 ? 3 : 1);
+    if (R.pitch == row && (R.kind != 2 || R.plane == row * sp.height)) { backend::d2h(frame, d_layout, R.bytes); return; }
+    std::vector<uint8_t> tmp(R.bytes);
+    backend::d2h(tmp.data(), d_layout, R.bytes);
+    for (int k = 0; k < (R.kind == 2 ? 3 : 1); k++)
+      for (int i = 0; i < sp.height; i++) memcpy((uint8_t*)frame + k * R.plane + i * R.pitch, &tmp[k * R.plane + i * R.pitch], row);
   }
 
   // planar 4:2:0 frame of input-depth samples in host memory -> device `orig` of stream s

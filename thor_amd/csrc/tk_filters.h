@@ -419,4 +419,281 @@ TK_DEV void layout_out_rows(const Plane3<PIX>& src, void* base, const PixLayout&
   }
 }
 
+// ---- RGB frames: colour conversion and 4:2:0 downsampling at the boundary (include/thor_hip.h: thor_hip_rgb_format) -------------------------------
+// What screen capture, renderers and tensor pipelines hold.  Staging an RGB frame is converting it to a planar 4:2:0 frame of input_bitdepth
+// samples and staging that; fetching is the inverse of the reconstruction rounded back to input_bitdepth.  Integers only; the coefficients are
+// derived once per (format, input_bitdepth) on the host (resolve_rgb) and travel by value.  The formulas are spelled out in include/thor_hip.h.
+enum { RGB_FWD_BITS = 24, RGB_INV_BITS = 20 };
+struct RgbFormat {  // a thor_hip_rgb_format resolved against a picture and an input depth
+  int kind;         // 0: four samples per pixel, 1: three samples per pixel, 2: three planes R, G, B
+  int lead;         // four samples per pixel: 1 when the unused one comes first (ARGB / ABGR)
+  int swap;         // packed: 1 when blue comes before red (BGRA / ABGR / BGR)
+  int sbytes;       // bytes per sample of the RGB side: 1 (depth 8) or 2
+  int msb;          // samples are value << msb (16 - depth when msb_aligned, else 0)
+  int maxv;         // 2^depth - 1
+  int site;         // 0: chroma at the centre of its 2x2 quad, 1: at the left column ([1 2 1] / 4 horizontally, left edge replicated)
+  size_t pitch, plane, bytes;   // bytes between rows, between planes (kind 2), from the base to the end of the frame
+  int oy, oc, maxo;             // luma offset, chroma offset, 2^input_bitdepth - 1
+  int yr, yg, yb, ur, ug, ub, vr, vg, vb;  // RGB -> Y'CbCr, RGB_FWD_BITS fractional bits; ur + ug + ub == vr + vg + vb == 0
+  int iy, rv, gu, gv, bu;                  // Y'CbCr -> RGB, RGB_INV_BITS fractional bits
+};
+
+// round(a / b) for a >= 0, b > 0, halves up
+static inline long long rgb_rdiv(long long a, long long b) { return (2 * a + b) / (2 * b); }
+
+// The caller's description against a width x height picture whose 4:2:0 samples have input_bitdepth bits.  false: the format is refused.
+static inline bool resolve_rgb(int order, int depth, int msb_aligned, int matrix, int full_range, int chroma_site, long long pitch, size_t plane_stride,
+                               int width, int height, int input_bitdepth, RgbFormat& R) {
+  static const int K[3][2] = {{2990, 1140}, {2126, 722}, {2627, 593}};  // Kr, Kb over 10000: BT.601, BT.709, BT.2020 (Kg = 10000 - Kr - Kb)
+  if (order < 0 || order > 6 || (depth != 8 && depth != 10 && depth != 12 && depth != 16)) return false;
+  if (msb_aligned < 0 || msb_aligned > 1 || (msb_aligned && depth != 10 && depth != 12)) return false;
+  if (matrix < 0 || matrix > 2 || full_range < 0 || full_range > 1 || chroma_site < 0 || chroma_site > 1 || pitch < 0) return false;
+  if (width < 16 || height < 16 || width % 8 || height % 8 || (input_bitdepth != 8 && input_bitdepth != 10 && input_bitdepth != 12)) return false;
+  R.kind = order < 4 ? 0 : order < 6 ? 1 : 2;
+  R.lead = order == 2 || order == 3;
+  R.swap = order == 1 || order == 3 || order == 5;
+  R.sbytes = depth > 8 ? 2 : 1;
+  R.msb = msb_aligned ? 16 - depth : 0;
+  R.maxv = (1 << depth) - 1;
+  R.site = chroma_site;
+  const size_t row = (size_t)width * R.sbytes * (R.kind == 0 ? 4 : R.kind == 1 ? 3 : 1);
+  R.pitch = pitch ? (size_t)pitch : row;
+  if (R.pitch < row || R.pitch % R.sbytes || plane_stride % R.sbytes || (plane_stride && R.kind != 2)) return false;
+  R.plane = R.kind == 2 ? (plane_stride ? plane_stride : R.pitch * height) : 0;
+  if (R.kind == 2 && R.plane < R.pitch * height) return false;
+  R.bytes = R.kind == 2 ? 2 * R.plane + R.pitch * height : R.pitch * height;
+  const int n = input_bitdepth;
+  const long long M = R.maxv, kr = K[matrix][0], kb = K[matrix][1], kg = 10000 - kr - kb;
+  const long long SY = full_range ? (1 << n) - 1 : 219 << (n - 8), SC = full_range ? (1 << n) - 1 : 224 << (n - 8);
+  R.oy = full_range ? 0 : 16 << (n - 8);
+  R.oc = 1 << (n - 1);
+  R.maxo = (1 << n) - 1;
+  const int F = RGB_FWD_BITS, G = RGB_INV_BITS;
+  R.yr = (int)rgb_rdiv((kr * SY) << F, 10000 * M);
+  R.yb = (int)rgb_rdiv((kb * SY) << F, 10000 * M);
+  R.yg = (int)rgb_rdiv(SY << F, M) - R.yr - R.yb;
+  R.ub = (int)rgb_rdiv(SC << F, 2 * M);
+  R.ur = -(int)rgb_rdiv((kr * SC) << F, 2 * (10000 - kb) * M);
+  R.ug = -R.ub - R.ur;
+  R.vr = (int)rgb_rdiv(SC << F, 2 * M);
+  R.vb = -(int)rgb_rdiv((kb * SC) << F, 2 * (10000 - kr) * M);
+  R.vg = -R.vr - R.vb;
+  R.iy = (int)rgb_rdiv(M << G, SY);
+  R.rv = (int)rgb_rdiv((2 * (10000 - kr) * M) << G, 10000 * SC);
+  R.bu = (int)rgb_rdiv((2 * (10000 - kb) * M) << G, 10000 * SC);
+  R.gu = -(int)rgb_rdiv((2 * kb * (10000 - kb) * M) << G, 10000 * kg * SC);
+  R.gv = -(int)rgb_rdiv((2 * kr * (10000 - kr) * M) << G, 10000 * kg * SC);
+  return true;
+}
+
+TK_DEV int rgb_clamp(long long v, int maxv) { return v < 0 ? 0 : v > maxv ? maxv : (int)v; }
+TK_DEV int rgb_luma(const RgbFormat& R, int r, int g, int b) {
+  const long long a = (long long)R.yr * r + (long long)R.yg * g + (long long)R.yb * b + ((long long)R.oy << RGB_FWD_BITS) + (1ll << (RGB_FWD_BITS - 1));
+  return rgb_clamp(a >> RGB_FWD_BITS, R.maxo);
+}
+// tr, tg, tb: the sums over the chroma sample's taps (weights adding up to 1 << taps_log2): one rounding for the whole sum
+TK_DEV int rgb_chroma(const RgbFormat& R, int cr, int cg, int cb, int tr, int tg, int tb, int taps_log2) {
+  const int sh = RGB_FWD_BITS + taps_log2;
+  const long long a = (long long)cr * tr + (long long)cg * tg + (long long)cb * tb + ((long long)R.oc << sh) + (1ll << (sh - 1));
+  return rgb_clamp(a >> sh, R.maxo);
+}
+TK_DEV void rgb_inverse(const RgbFormat& R, int y, int u, int v, int& r, int& g, int& b) {
+  const long long l = (long long)R.iy * (y - R.oy) + (1ll << (RGB_INV_BITS - 1));
+  r = rgb_clamp((l + (long long)R.rv * (v - R.oc)) >> RGB_INV_BITS, R.maxv);
+  g = rgb_clamp((l + (long long)R.gu * (u - R.oc) + (long long)R.gv * (v - R.oc)) >> RGB_INV_BITS, R.maxv);
+  b = rgb_clamp((l + (long long)R.bu * (u - R.oc)) >> RGB_INV_BITS, R.maxv);
+}
+
+// Pixel x of the row at `row`, sample by sample.
+template <typename SRC> TK_DEV void rgb_load_px(const uint8_t* row, const RgbFormat& R, int x, int& r, int& g, int& b) {
+  if (R.kind == 2) {
+    r = ((const SRC*)row)[x] >> R.msb; g = ((const SRC*)(row + R.plane))[x] >> R.msb; b = ((const SRC*)(row + 2 * R.plane))[x] >> R.msb;
+    return;
+  }
+  const SRC* p = (const SRC*)row + (size_t)x * (R.kind == 0 ? 4 : 3) + R.lead;
+  const int c0 = p[0] >> R.msb, c2 = p[2] >> R.msb;
+  r = R.swap ? c2 : c0; g = p[1] >> R.msb; b = R.swap ? c0 : c2;
+}
+template <typename DST> TK_DEV void rgb_store_px(uint8_t* row, const RgbFormat& R, int x, int r, int g, int b) {
+  if (R.kind == 2) {
+    ((DST*)row)[x] = (DST)(r << R.msb); ((DST*)(row + R.plane))[x] = (DST)(g << R.msb); ((DST*)(row + 2 * R.plane))[x] = (DST)(b << R.msb);
+    return;
+  }
+  DST* p = (DST*)row + (size_t)x * (R.kind == 0 ? 4 : 3);
+  if (R.kind == 0) p[R.lead ? 0 : 3] = (DST)(R.maxv << R.msb);
+  p += R.lead;
+  p[0] = (DST)((R.swap ? b : r) << R.msb); p[1] = (DST)(g << R.msb); p[2] = (DST)((R.swap ? r : b) << R.msb);
+}
+
+// Pixels per lane step.  With whole vectors: 16 bytes of a four-sample row (4 pixels of bytes, 2 of 16-bit words), the three dwords that hold as many
+// pixels of a three-sample row, 16 bytes of each plane of a planar frame; sample by sample: one 2x2 quad.
+template <typename S, int KIND, bool VEC> struct RgbRun { static constexpr int P = !VEC ? 2 : KIND == 2 ? 16 / (int)sizeof(S) : 4 / (int)sizeof(S); };
+
+// Sample j of the 3 * P samples that three dwords hold (little-endian).
+template <typename S> TK_DEV int rgb_dword_sample(const uint32_t* w, int j) {
+  constexpr int per = 4 / (int)sizeof(S);
+  return (int)((w[j / per] >> (8 * (int)sizeof(S) * (j % per))) & (sizeof(S) == 1 ? 0xffu : 0xffffu));
+}
+
+// Luma rows 2 * crow and 2 * crow + 1, pixels x0 .. x0 + P - 1, with their P / 2 chroma samples: RGB -> planes.  x0 is a multiple of P.
+template <typename SRC, typename PIX, int KIND, bool VEC>
+TK_DEV void rgb_in_span(const uint8_t* base, const RgbFormat& R, const Plane3<PIX>& dst, int up, int crow, int x0) {
+  constexpr int P = RgbRun<SRC, KIND, VEC>::P;
+  int r[2][P], g[2][P], b[2][P], lr[2] = {0, 0}, lg[2] = {0, 0}, lb[2] = {0, 0};
+  for (int q = 0; q < 2; q++) {
+    const uint8_t* row = base + (size_t)(2 * crow + q) * R.pitch;
+    if constexpr (!VEC) {
+      for (int k = 0; k < P; k++) rgb_load_px<SRC>(row, R, x0 + k, r[q][k], g[q][k], b[q][k]);
+    } else if constexpr (KIND == 0) {
+      const LayoutVec<SRC, 4 * P> a = *(const LayoutVec<SRC, 4 * P>*)(row + (size_t)x0 * 4 * sizeof(SRC));
+      for (int k = 0; k < P; k++) {
+        const int c0 = (R.lead ? a.v[4 * k + 1] : a.v[4 * k]) >> R.msb, c2 = (R.lead ? a.v[4 * k + 3] : a.v[4 * k + 2]) >> R.msb;
+        r[q][k] = R.swap ? c2 : c0; g[q][k] = (R.lead ? a.v[4 * k + 2] : a.v[4 * k + 1]) >> R.msb; b[q][k] = R.swap ? c0 : c2;
+      }
+    } else if constexpr (KIND == 1) {
+      const uint32_t* wp = (const uint32_t*)(row + (size_t)x0 * 3 * sizeof(SRC));
+      const uint32_t w[3] = {wp[0], wp[1], wp[2]};
+      for (int k = 0; k < P; k++) {
+        const int c0 = rgb_dword_sample<SRC>(w, 3 * k) >> R.msb, c2 = rgb_dword_sample<SRC>(w, 3 * k + 2) >> R.msb;
+        r[q][k] = R.swap ? c2 : c0; g[q][k] = rgb_dword_sample<SRC>(w, 3 * k + 1) >> R.msb; b[q][k] = R.swap ? c0 : c2;
+      }
+    } else {
+      const LayoutVec<SRC, P> ar = *(const LayoutVec<SRC, P>*)(row + (size_t)x0 * sizeof(SRC));
+      const LayoutVec<SRC, P> ag = *(const LayoutVec<SRC, P>*)(row + R.plane + (size_t)x0 * sizeof(SRC));
+      const LayoutVec<SRC, P> ab = *(const LayoutVec<SRC, P>*)(row + 2 * R.plane + (size_t)x0 * sizeof(SRC));
+      for (int k = 0; k < P; k++) { r[q][k] = ar.v[k] >> R.msb; g[q][k] = ag.v[k] >> R.msb; b[q][k] = ab.v[k] >> R.msb; }
+    }
+    if (R.site) rgb_load_px<SRC>(row, R, x0 ? x0 - 1 : 0, lr[q], lg[q], lb[q]);  // the tap one column back, within the same rows
+  }
+  PIX yo[2][P], uo[P / 2], vo[P / 2];
+  for (int q = 0; q < 2; q++)
+    for (int k = 0; k < P; k++) yo[q][k] = (PIX)(rgb_luma(R, r[q][k], g[q][k], b[q][k]) << up);
+  for (int j = 0; j < P / 2; j++) {
+    int tr = 0, tg = 0, tb = 0;
+    for (int q = 0; q < 2; q++) {
+      if (R.site) {
+        tr += (j ? r[q][2 * j - 1] : lr[q]) + 2 * r[q][2 * j] + r[q][2 * j + 1];
+        tg += (j ? g[q][2 * j - 1] : lg[q]) + 2 * g[q][2 * j] + g[q][2 * j + 1];
+        tb += (j ? b[q][2 * j - 1] : lb[q]) + 2 * b[q][2 * j] + b[q][2 * j + 1];
+      } else {
+        tr += r[q][2 * j] + r[q][2 * j + 1]; tg += g[q][2 * j] + g[q][2 * j + 1]; tb += b[q][2 * j] + b[q][2 * j + 1];
+      }
+    }
+    uo[j] = (PIX)(rgb_chroma(R, R.ur, R.ug, R.ub, tr, tg, tb, R.site ? 3 : 2) << up);
+    vo[j] = (PIX)(rgb_chroma(R, R.vr, R.vg, R.vb, tr, tg, tb, R.site ? 3 : 2) << up);
+  }
+  PIX* dy = dst.y + (size_t)(2 * crow) * dst.sy + x0;
+  PIX* du = dst.u + (size_t)crow * dst.sc + x0 / 2;
+  PIX* dv = dst.v + (size_t)crow * dst.sc + x0 / 2;
+  if constexpr (VEC) {  // plane rows are 16-byte aligned and x0 is a multiple of P
+    LayoutVec<PIX, P> o0, o1;
+    LayoutVec<PIX, P / 2> ou, ov;
+    for (int k = 0; k < P; k++) { o0.v[k] = yo[0][k]; o1.v[k] = yo[1][k]; }
+    for (int j = 0; j < P / 2; j++) { ou.v[j] = uo[j]; ov.v[j] = vo[j]; }
+    *(LayoutVec<PIX, P>*)dy = o0; *(LayoutVec<PIX, P>*)(dy + dst.sy) = o1;
+    *(LayoutVec<PIX, P / 2>*)du = ou; *(LayoutVec<PIX, P / 2>*)dv = ov;
+  } else {
+    for (int k = 0; k < P; k++) { dy[k] = yo[0][k]; dy[dst.sy + k] = yo[1][k]; }
+    for (int j = 0; j < P / 2; j++) { du[j] = uo[j]; dv[j] = vo[j]; }
+  }
+}
+
+// The same span the other way: planes -> RGB, chroma replicated over its quad, the reconstruction rounded back to the input depth first.
+template <typename PIX, typename DST, int KIND, bool VEC>
+TK_DEV void rgb_out_span(const Plane3<PIX>& src, uint8_t* base, const RgbFormat& R, int shift, int crow, int x0) {
+  constexpr int P = RgbRun<DST, KIND, VEC>::P;
+  int y[2][P], u[P / 2], v[P / 2];
+  const PIX* sy = src.y + (size_t)(2 * crow) * src.sy + x0;
+  const PIX* su = src.u + (size_t)crow * src.sc + x0 / 2;
+  const PIX* sv = src.v + (size_t)crow * src.sc + x0 / 2;
+  if constexpr (VEC) {
+    const LayoutVec<PIX, P> a0 = *(const LayoutVec<PIX, P>*)sy, a1 = *(const LayoutVec<PIX, P>*)(sy + src.sy);
+    const LayoutVec<PIX, P / 2> au = *(const LayoutVec<PIX, P / 2>*)su, av = *(const LayoutVec<PIX, P / 2>*)sv;
+    for (int k = 0; k < P; k++) { y[0][k] = a0.v[k]; y[1][k] = a1.v[k]; }
+    for (int j = 0; j < P / 2; j++) { u[j] = au.v[j]; v[j] = av.v[j]; }
+  } else {
+    for (int k = 0; k < P; k++) { y[0][k] = sy[k]; y[1][k] = sy[src.sy + k]; }
+    for (int j = 0; j < P / 2; j++) { u[j] = su[j]; v[j] = sv[j]; }
+  }
+  if (shift > 0) {
+    for (int k = 0; k < P; k++) { y[0][k] = depth_round(y[0][k], shift, R.maxo); y[1][k] = depth_round(y[1][k], shift, R.maxo); }
+    for (int j = 0; j < P / 2; j++) { u[j] = depth_round(u[j], shift, R.maxo); v[j] = depth_round(v[j], shift, R.maxo); }
+  }
+  for (int q = 0; q < 2; q++) {
+    uint8_t* row = base + (size_t)(2 * crow + q) * R.pitch;
+    int r[P], g[P], b[P];
+    for (int k = 0; k < P; k++) rgb_inverse(R, y[q][k], u[k / 2], v[k / 2], r[k], g[k], b[k]);
+    if constexpr (!VEC) {
+      for (int k = 0; k < P; k++) rgb_store_px<DST>(row, R, x0 + k, r[k], g[k], b[k]);
+    } else if constexpr (KIND == 0) {
+      LayoutVec<DST, 4 * P> o;
+      const int one = R.maxv << R.msb;
+      for (int k = 0; k < P; k++) {
+        const int c0 = (R.swap ? b[k] : r[k]) << R.msb, c1 = g[k] << R.msb, c2 = (R.swap ? r[k] : b[k]) << R.msb;
+        o.v[4 * k] = (DST)(R.lead ? one : c0); o.v[4 * k + 1] = (DST)(R.lead ? c0 : c1);
+        o.v[4 * k + 2] = (DST)(R.lead ? c1 : c2); o.v[4 * k + 3] = (DST)(R.lead ? c2 : one);
+      }
+      *(LayoutVec<DST, 4 * P>*)(row + (size_t)x0 * 4 * sizeof(DST)) = o;
+    } else if constexpr (KIND == 1) {
+      constexpr int per = 4 / (int)sizeof(DST);
+      uint32_t w[3] = {0, 0, 0};
+      for (int k = 0; k < P; k++) {
+        const int c[3] = {(R.swap ? b[k] : r[k]) << R.msb, g[k] << R.msb, (R.swap ? r[k] : b[k]) << R.msb};
+        for (int i = 0; i < 3; i++) w[(3 * k + i) / per] |= (uint32_t)c[i] << (8 * (int)sizeof(DST) * ((3 * k + i) % per));
+      }
+      uint32_t* wp = (uint32_t*)(row + (size_t)x0 * 3 * sizeof(DST));
+      wp[0] = w[0]; wp[1] = w[1]; wp[2] = w[2];
+    } else {
+      LayoutVec<DST, P> orr, og, ob;
+      for (int k = 0; k < P; k++) { orr.v[k] = (DST)(r[k] << R.msb); og.v[k] = (DST)(g[k] << R.msb); ob.v[k] = (DST)(b[k] << R.msb); }
+      *(LayoutVec<DST, P>*)(row + (size_t)x0 * sizeof(DST)) = orr;
+      *(LayoutVec<DST, P>*)(row + R.plane + (size_t)x0 * sizeof(DST)) = og;
+      *(LayoutVec<DST, P>*)(row + 2 * R.plane + (size_t)x0 * sizeof(DST)) = ob;
+    }
+  }
+}
+
+// Whether the rows of the RGB side take whole vectors: 16-byte aligned rows (and planes) for four samples per pixel and for planes, 4-byte aligned
+// rows for three samples per pixel.
+TK_DEV bool rgb_rows_aligned(const void* base, const RgbFormat& R) {
+  return ((((uintptr_t)base) | R.pitch | R.plane) & (R.kind == 1 ? 3 : 15)) == 0;
+}
+
+// An RGB frame at `base` (SRC = uint8_t for depth 8, uint16_t otherwise) -> the engine's planes, input_bitdepth samples << up.  One work item per
+// pair of luma rows with its chroma row; `lane`/`nlanes` stride along it in runs of RgbRun::P pixels, what is left of the row quad by quad.
+template <typename SRC, typename PIX, int KIND>
+TK_DEV void rgb_in_kind(const uint8_t* b, const RgbFormat& R, const Plane3<PIX>& dst, int width, int height, int up, int gid, int gsize, int lane, int nlanes) {
+  constexpr int P = RgbRun<SRC, KIND, true>::P;
+  const int nv = rgb_rows_aligned(b, R) ? width / P : 0;
+  for (int it = gid; it < height / 2; it += gsize) {
+    for (int i = lane; i < nv; i += nlanes) rgb_in_span<SRC, PIX, KIND, true>(b, R, dst, up, it, i * P);
+    for (int x = nv * P + 2 * lane; x < width; x += 2 * nlanes) rgb_in_span<SRC, PIX, KIND, false>(b, R, dst, up, it, x);
+  }
+}
+template <typename SRC, typename PIX>
+TK_DEV void rgb_in_rows(const void* base, const RgbFormat& R, const Plane3<PIX>& dst, int width, int height, int up, int gid, int gsize, int lane, int nlanes) {
+  const uint8_t* b = (const uint8_t*)base;
+  if (R.kind == 0) rgb_in_kind<SRC, PIX, 0>(b, R, dst, width, height, up, gid, gsize, lane, nlanes);
+  else if (R.kind == 1) rgb_in_kind<SRC, PIX, 1>(b, R, dst, width, height, up, gid, gsize, lane, nlanes);
+  else rgb_in_kind<SRC, PIX, 2>(b, R, dst, width, height, up, gid, gsize, lane, nlanes);
+}
+
+// The engine's planes -> an RGB frame at `base` (DST = uint8_t for depth 8, uint16_t otherwise); shift = bitdepth - input_bitdepth.  Same work split.
+template <typename PIX, typename DST, int KIND>
+TK_DEV void rgb_out_kind(const Plane3<PIX>& src, uint8_t* b, const RgbFormat& R, int width, int height, int shift, int gid, int gsize, int lane, int nlanes) {
+  constexpr int P = RgbRun<DST, KIND, true>::P;
+  const int nv = rgb_rows_aligned(b, R) ? width / P : 0;
+  for (int it = gid; it < height / 2; it += gsize) {
+    for (int i = lane; i < nv; i += nlanes) rgb_out_span<PIX, DST, KIND, true>(src, b, R, shift, it, i * P);
+    for (int x = nv * P + 2 * lane; x < width; x += 2 * nlanes) rgb_out_span<PIX, DST, KIND, false>(src, b, R, shift, it, x);
+  }
+}
+template <typename PIX, typename DST>
+TK_DEV void rgb_out_rows(const Plane3<PIX>& src, void* base, const RgbFormat& R, int width, int height, int shift, int gid, int gsize, int lane, int nlanes) {
+  uint8_t* b = (uint8_t*)base;
+  if (R.kind == 0) rgb_out_kind<PIX, DST, 0>(src, b, R, width, height, shift, gid, gsize, lane, nlanes);
+  else if (R.kind == 1) rgb_out_kind<PIX, DST, 1>(src, b, R, width, height, shift, gid, gsize, lane, nlanes);
+  else rgb_out_kind<PIX, DST, 2>(src, b, R, width, height, shift, gid, gsize, lane, nlanes);
+}
+
 }  // namespace tk

@@ -1,10 +1,14 @@
 /* thorenc_hip.c - minimal C front end over the libthor_hip.so sequence API (include/thor_hip.h).
  * Usage mirrors the reference Thorenc (enc/strings.c:287-356) for the options this path honours:
  *   thorenc_hip -cf config.txt -if in.yuv -width W -height H -qp Q -n N [-skip K] [-f fps]
- *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-pixfmt i420|nv12|nv21|p010] [-name value ...]
+ *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-pixfmt i420|nv12|nv21|p010|rgba|bgra|rgb24|bgr24] [-name value ...]
+ *               [-rgbmatrix 601|709|2020] [-rgbrange limited|full] [-rgbsite centre|left]
  * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
  * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
  * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
+ * rgba / bgra / rgb24 / bgr24: the files hold RGB frames - one byte per channel with 8-bit input, else 16-bit words with the value in the low
+ * bits - converted on the device (thor_hip_stage_frame_rgb / thor_hip_get_recon_rgb) with -rgbmatrix (default 709), -rgbrange (limited) and
+ * -rgbsite (left).
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -26,16 +30,16 @@ static double now_s(void) {
 }
 
 /* thor_hip_encode_staged_run's callback: keep the reconstructions of the frames that just completed (display order) */
-struct done_ctx { thor_hip_encoder* e; unsigned char** recs; FILE** fr; int n; size_t fsz; const thor_hip_frame_layout* lay; };
-static void get_recon(thor_hip_encoder* e, int s, unsigned char* r, const thor_hip_frame_layout* lay) {
-  if (lay) thor_hip_get_recon_layout(e, s, r, lay, 0); else thor_hip_get_recon(e, s, r);
+struct done_ctx { thor_hip_encoder* e; unsigned char** recs; FILE** fr; int n; size_t fsz; const thor_hip_frame_layout* lay; const thor_hip_rgb_format* rgb; };
+static void get_recon(thor_hip_encoder* e, int s, unsigned char* r, const thor_hip_frame_layout* lay, const thor_hip_rgb_format* rgb) {
+  if (rgb) thor_hip_get_recon_rgb(e, s, r, rgb, 0); else if (lay) thor_hip_get_recon_layout(e, s, r, lay, 0); else thor_hip_get_recon(e, s, r);
 }
 static void frames_done(void* user, int first, int count) {
   struct done_ctx* c = (struct done_ctx*)user;
   for (int s = first; s < first + count; s++)
     if (c->fr[s]) {
       unsigned char* r = (unsigned char*)malloc(c->fsz);
-      get_recon(c->e, s, r, c->lay);
+      get_recon(c->e, s, r, c->lay, c->rgb);
       c->recs[(size_t)s * c->n + thor_hip_last_display_index(c->e, s)] = r;
     }
 }
@@ -45,6 +49,7 @@ int main(int argc, char** argv) {
   const char *inf = NULL, *of = NULL, *rf = NULL;
   const char* statf = NULL;
   const char* pixfmt = "i420";
+  const char *rgbmatrix = "709", *rgbrange = "limited", *rgbsite = "left";
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -62,6 +67,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-snrcalc")) snrcalc = atoi(v);
     else if (!strcmp(k, "-stat")) statf = v;
     else if (!strcmp(k, "-pixfmt")) pixfmt = v;
+    else if (!strcmp(k, "-rgbmatrix")) rgbmatrix = v;
+    else if (!strcmp(k, "-rgbrange")) rgbrange = v;
+    else if (!strcmp(k, "-rgbsite")) rgbsite = v;
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -71,14 +79,26 @@ int main(int argc, char** argv) {
   if (p.input_bitdepth > p.bitdepth) { fprintf(stderr, "Run-time error...\ninput_bitdepth %d above bitdepth %d is not implemented by this path\n...now exiting to system...\n", p.input_bitdepth, p.bitdepth); return 2; }
   thor_hip_frame_layout layout = {sizeof(thor_hip_frame_layout), THOR_HIP_CHROMA_PLANAR, 0, 0, 0, 0, 0};
   const thor_hip_frame_layout* lay = strcmp(pixfmt, "i420") ? &layout : NULL; /* i420: the calls the files always took */
+  thor_hip_rgb_format rgbfmt = {sizeof(thor_hip_rgb_format), 0, 8, 0, 0, 0, 0, 0, 0};
+  const thor_hip_rgb_format* rgb = NULL; /* -pixfmt rgba|bgra|rgb24|bgr24: the files hold RGB frames, the device converts */
   if (!strcmp(pixfmt, "nv12")) layout.chroma = THOR_HIP_CHROMA_UV;
   else if (!strcmp(pixfmt, "nv21")) layout.chroma = THOR_HIP_CHROMA_VU;
   else if (!strcmp(pixfmt, "p010")) { layout.chroma = THOR_HIP_CHROMA_UV; layout.msb_aligned = 1; }
+  else if (!strcmp(pixfmt, "rgba") || !strcmp(pixfmt, "bgra") || !strcmp(pixfmt, "rgb24") || !strcmp(pixfmt, "bgr24")) {
+    lay = NULL;
+    rgb = &rgbfmt;
+    rgbfmt.order = !strcmp(pixfmt, "rgba") ? THOR_HIP_RGB_RGBA : !strcmp(pixfmt, "bgra") ? THOR_HIP_RGB_BGRA : !strcmp(pixfmt, "rgb24") ? THOR_HIP_RGB_RGB : THOR_HIP_RGB_BGR;
+    rgbfmt.depth = p.input_bitdepth > 8 ? 16 : 8;
+    rgbfmt.matrix = !strcmp(rgbmatrix, "601") ? THOR_HIP_MATRIX_BT601 : !strcmp(rgbmatrix, "709") ? THOR_HIP_MATRIX_BT709 : !strcmp(rgbmatrix, "2020") ? THOR_HIP_MATRIX_BT2020 : -1;
+    rgbfmt.full_range = !strcmp(rgbrange, "full") ? 1 : !strcmp(rgbrange, "limited") ? 0 : -1;
+    rgbfmt.chroma_site = !strcmp(rgbsite, "left") ? 1 : !strcmp(rgbsite, "centre") ? 0 : -1;
+    if (!thor_hip_rgb_bytes_for(p.width, p.height, &rgbfmt)) { fprintf(stderr, "Run-time error...\n-pixfmt %s with -rgbmatrix %s -rgbrange %s -rgbsite %s is not a format of this path\n...now exiting to system...\n", pixfmt, rgbmatrix, rgbrange, rgbsite); return 2; }
+  }
   else if (lay) { fprintf(stderr, "Run-time error...\noption -pixfmt %s is unknown\n...now exiting to system...\n", pixfmt); return 2; }
   if (lay && p.input_bitdepth <= 8 && layout.msb_aligned) { fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", pixfmt); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
-  size_t fsz = thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth */
+  size_t fsz = rgb ? thor_hip_rgb_bytes(e, rgb) : thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth, or RGB frames */
   unsigned char* frame = (unsigned char*)malloc(fsz);
   thor_hip_set_frame_distortion(e, snrcalc != 0);
   for (int s = 0; s < S; s++)
@@ -86,7 +106,7 @@ int main(int argc, char** argv) {
       size_t idx = (size_t)skip + (size_t)s * n + f;
       if (wrap > 0) idx %= (size_t)wrap;
       if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame, 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); return 4; }
-      if (lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
+      if (rgb ? thor_hip_stage_frame_rgb(e, s, f, frame, rgb, 0) : lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
     }
   FILE** fr = (FILE**)calloc(S, sizeof(FILE*));
   char name[4096];
@@ -104,7 +124,7 @@ int main(int argc, char** argv) {
   double t0 = now_s(), tenc = 0;
   int coded = 0;
   if (S > 1 && getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER"))) {
-    struct done_ctx ctx = {e, recs, fr, n, fsz, lay};
+    struct done_ctx ctx = {e, recs, fr, n, fsz, lay, rgb};
     double a = now_s();
     if (thor_hip_encode_staged_run(e, n, frames_done, &ctx)) { fprintf(stderr, "encode failed\n"); return 5; }
     tenc = now_s() - a;
@@ -122,7 +142,7 @@ int main(int argc, char** argv) {
     for (int s = 0; s < S; s++)
       if (fr[s]) {
         unsigned char* r = (unsigned char*)malloc(fsz);
-        get_recon(e, s, r, lay);
+        get_recon(e, s, r, lay, rgb);
         recs[(size_t)s * n + slots[s]] = r;
       }
   }
