@@ -374,6 +374,33 @@ int thor_hip_kat_motion_estimate_bi(const void* cur, const void* ref0, const voi
  * items: chroma[i] 0 luma / 1 chroma, size[i] (luma 8 / 16 / 32, chroma 4 / 8 / 16), qp[i], thr[i] (early_skip_thr); org / pred: n blocks of 32x32 samples
  * holding the size x size block in their top-left corner.  out[i]: 1 = significant.  Known answers: tests/golden/gen_kat7.py -> kat7.npz. */
 int thor_hip_kat_early_skip(const int* chroma, const void* org, const void* pred, const int* size, const int* qp, const float* thr, int bitdepth, int n, int* out);
+/* The neighbour context of a coding block (thor_amd/csrc/tk_block_ctx.h) on `n` items of one cell grid, one wavefront per item, against the reference's
+ * get_mv_pred, get_mv_skip / get_mv_merge (common/inter_prediction.c:413-834), find_block_contexts (common/common_block.c:283) and get_upright_available /
+ * get_downleft_available (common/common_block.h:60-95): tests/golden/gen_kat11.py -> kat11.npz.  cells: ncells records in raster order, cell_stride per row
+ * (rows past the frame's height / 4 are what a block that hangs over the bottom edge reads).  par[6*i..]: ypos, xpos, size (8..sb), frame width (= 4 *
+ * cell_stride), frame height, superblock size (64 / 128); positions lie on the size grid inside the frame and ncells covers the rows down to ypos + size.
+ * out[23*i..]: get_mv_pred x, y; number of candidates; candidate 0 and 1 as mv0.x, mv0.y, mv1.x, mv1.y, ref0, ref1, dir (zeros when not returned);
+ * ctx_cbp, ctx_index with enable 0, then with enable 1; up-right and down-left availability. */
+int thor_hip_kat_block_ctx(const thor_hip_cell* cells, long long ncells, int cell_stride, int n, const int* par, int* out);
+/* ssd_part / ssd_total / rd_cost (thor_amd/csrc/tk_block_rd.h) on `n` items against cost_calc (enc/encode_block.c:916-926): tests/golden/gen_kat11.py.  org / rec:
+ * pools of nsamp samples; item i owns a compact 4:2:0 block at par's `off` (Y size x size, U, V, stride = size) in both.  par[7*i..]: size (8..128), bw, bh
+ * (multiples of 8 up to size: the part inside the frame), nbits (0..2^20), off (multiple of 16), skew (bytes from a 16-byte boundary to the original's first
+ * sample, a whole number of samples below 16), stride (of the original's luma rows in samples, even, at least bw).  The originals are laid out as planes with
+ * that skew and stride; blocks up to the size the engine keeps in LDS are copied there as the engine does.  out[4*i..]: luma SSD from the global-memory
+ * instance, from the LDS instance (all ones for larger blocks), rd_cost, rd_cost with the luma SSD passed in. */
+/* Largest coding-block size whose sample buffers this build keeps in LDS (16 or 32): the blocks for which thor_hip_kat_block_cost runs the LDS instances. */
+int thor_hip_kat_lds_block(void);
+int thor_hip_kat_block_cost(int n, const int* par, const double* lambda, const void* org, const void* rec, long long nsamp, int bitdepth, unsigned long long* out);
+/* intra_sad_search (thor_amd/csrc/tk_block_search.h) on `n` items against search_intra_prediction_params (enc/encode_block.c:928-1031): tests/golden/gen_kat11.py.
+ * plane: the reconstructed luma plane, width x height samples (multiples of 8), stride = width; org: pool of nsamp samples holding each item's compact original
+ * block (stride = size).  par[6*i..]: ypos, xpos (on the size grid, the block inside the plane), size (8..64), superblock size (64 / 128), num_intra_modes
+ * (4 / 10), off (multiple of 16).  Up-right / down-left availability comes from the position, as in the encoder.  out[2*i..]: intra mode, SAD. */
+int thor_hip_kat_intra_search(int n, const int* par, const void* plane, int width, int height, const void* org, long long nsamp, int bitdepth, int* out);
+/* build_org8 (2 * org - pred, saturated: the original of a bi-prediction search step) on `n` items.  org / pred: pools of nsamp samples, item i owns a compact
+ * size x size block at par's `off` in both; par[4*i..]: size (8..128), off (multiple of 16), skew, stride (of the original, laid out as for
+ * thor_hip_kat_block_cost).  out_global / out_lds: pools of nsamp samples, read and written back whole; the item's result lands at `off` - out_global from the
+ * global-memory instance, out_lds from the LDS instance (blocks up to thor_hip_kat_lds_block() only; larger ones leave it untouched). */
+int thor_hip_kat_build_org8(int n, const int* par, const void* org, const void* pred, long long nsamp, int bitdepth, void* out_global, void* out_lds);
 /* The block syntax writer and its bit counter (thor_amd/csrc/tk_bits.h) on `n` items, one wavefront per item, against bit strings recorded from the reference's
  * put_vlc (enc/putvlc.c:73-160), write_mv (enc/write_bits.c:123-143), write_coeff (:145-241), write_super_mode (:257-358) and write_block (:360-600):
  * tests/golden/gen_kat9.py -> kat9.npz.  Bit strings are arrays of 32-bit words, word w = bits [32w, 32w + 32), first bit in the MSB; every item owns `words`

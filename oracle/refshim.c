@@ -203,7 +203,57 @@ void SHIM(ref_cdef_mse)(SAMPLE* rec_yuv, SAMPLE* org_yuv, const uint8_t* mode, i
   cdef_shim_close(&c);
 }
 
+/* cost_calc (enc/encode_block.c:916, file-static) as mode_decision_rdo calls it (tests/golden/gen_kat11.py -> kat11.npz): org / rec are compact blocks - Y size x size,
+ * then U and V (size / 2)^2 each, stride = size - copied into two yuv_block_t, whose planes are arrays of MAX_SB_SIZE^2 samples; sub = 1 (4:2:0); use_simd = 1
+ * is what the encoder executes (ssd_calc takes ssd_calc_simd for square blocks wider than 4). */
+uint32_t SHIM(ref_cost_calc)(const SAMPLE* org, const SAMPLE* rec, int size, int width, int height, int nbits, double lambda, int bitdepth) {
+  static yuv_block_t o __attribute__((aligned(32))), r __attribute__((aligned(32)));
+  const int n = size * size, c = n / 4;
+  memcpy(o.y, org, n * sizeof(SAMPLE)); memcpy(o.u, org + n, c * sizeof(SAMPLE)); memcpy(o.v, org + n + c, c * sizeof(SAMPLE));
+  memcpy(r.y, rec, n * sizeof(SAMPLE)); memcpy(r.u, rec + n, c * sizeof(SAMPLE)); memcpy(r.v, rec + n + c, c * sizeof(SAMPLE));
+  use_simd = 1;
+  return cost_calc(&o, &r, size, width, height, 1, nbits, lambda, bitdepth);
+}
+
+/* search_intra_prediction_params (enc/encode_block.c:928, file-static) as mode_decision_rdo calls it: org_y a compact size x size block, plane the reconstructed
+ * luma plane of fwidth x fheight samples with stride fwidth.  It reads rec->y, rec->stride_y and block_pos only.  Returns the SAD, *mode the intra_mode_t. */
+int SHIM(ref_search_intra)(const SAMPLE* org_y, SAMPLE* plane, int fwidth, int fheight, int ypos, int xpos, int size, int sb_size, int num_intra_modes, int bitdepth, int* mode) {
+  static SAMPLE o[MAX_SB_SIZE * MAX_SB_SIZE] __attribute__((aligned(32)));
+  yuv_frame_t rec;
+  block_pos_t bp;
+  intra_mode_t m = MODE_DC;
+  memset(&rec, 0, sizeof rec); memset(&bp, 0, sizeof bp);
+  memcpy(o, org_y, size * size * sizeof(SAMPLE));
+  rec.y = plane; rec.stride_y = fwidth; rec.width = fwidth; rec.height = fheight;
+  bp.ypos = (uint16_t)ypos; bp.xpos = (uint16_t)xpos; bp.size = bp.bwidth = bp.bheight = (uint8_t)size; bp.sb_size = (uint8_t)sb_size;
+  use_simd = 1;
+  int sad = search_intra_prediction_params(o, &rec, &bp, fwidth, fheight, num_intra_modes, &m, bitdepth);
+  *mode = (int)m;
+  return sad;
+}
+/* The ten predictions that search weighs, by the functions it calls: out[mode * size * size ..], mode = intra_mode_t. */
+void SHIM(ref_intra_preds)(SAMPLE* plane, int fwidth, int fheight, int ypos, int xpos, int size, int sb_size, int bitdepth, SAMPLE* out) {
+  SAMPLE left_[2 * MAX_TR_SIZE + 2], top_[2 * MAX_TR_SIZE + 2], top_left;
+  SAMPLE *left = left_ + 1, *top = top_ + 1;
+  const int n = size * size;
+  const int ur = get_upright_available(ypos, xpos, size, size, fwidth, fheight, sb_size), dl = get_downleft_available(ypos, xpos, size, size, fwidth, fheight, sb_size);
+  TEMPLATE(make_top_and_left)(left, top, &top_left, &plane[ypos * fwidth + xpos], fwidth, NULL, 0, 0, 0, ypos, xpos, size, ur, dl, 0, bitdepth);
+  TEMPLATE(get_dc_pred)(left, top, size, out + MODE_DC * n, size, bitdepth);
+  TEMPLATE(get_hor_pred)(left, size, out + MODE_HOR * n, size);
+  TEMPLATE(get_ver_pred)(top, size, out + MODE_VER * n, size);
+  TEMPLATE(get_planar_pred)(left, top, top_left, size, out + MODE_PLANAR * n, size, bitdepth);
+  TEMPLATE(get_upleft_pred)(left, top, top_left, size, out + MODE_UPLEFT * n, size);
+  TEMPLATE(get_upright_pred)(top, size, out + MODE_UPRIGHT * n, size);
+  TEMPLATE(get_upupright_pred)(top, size, out + MODE_UPUPRIGHT * n, size);
+  TEMPLATE(get_upupleft_pred)(left, top, top_left, size, out + MODE_UPUPLEFT * n, size);
+  TEMPLATE(get_upleftleft_pred)(left, top, top_left, size, out + MODE_UPLEFTLEFT * n, size);
+  TEMPLATE(get_downleftleft_pred)(left, size, out + MODE_DOWNLEFTLEFT * n, size);
+}
+
 #ifndef REFSHIM_HBD
+/* get_upright_available / get_downleft_available (common/common_block.h:60-95, static inline) as every caller uses them */
+int ref_upright_available(int ypos, int xpos, int bwidth, int bheight, int fwidth, int fheight, int sb_size) { return get_upright_available(ypos, xpos, bwidth, bheight, fwidth, fheight, sb_size); }
+int ref_downleft_available(int ypos, int xpos, int bwidth, int bheight, int fwidth, int fheight, int sb_size) { return get_downleft_available(ypos, xpos, bwidth, bheight, fwidth, fheight, sb_size); }
 void ref_init(int simd) { use_simd = simd; }
 unsigned ref_sad_calc(uint8_t* a, uint8_t* b, int astride, int bstride, int w, int h) { return sad_calc(a, b, astride, bstride, w, h); }
 int ref_quantize(int16_t* coeff, int16_t* coeffq, int qp, int size, int coeff_block_type) {

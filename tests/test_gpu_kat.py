@@ -152,6 +152,31 @@ def test_code_tu_hbd_matches_reference_kat(bd):
 
 
 @pytest.mark.parametrize('bd', [10, 12])
+def test_code_tu_hbd_edge_cases_vs_oracle_c(bd):
+    """The extremes of test_code_tu_random_edge_cases_vs_oracle_c on 16-bit samples: residuals of +-(2^bd - 1) everywhere, checkerboards between 0 and the
+    maximum, empty blocks and random ones - the wave-parallel transforms and quantiser against orc_code_tu16 (pinned to the reference in tests/test_oracle_c.py)."""
+    import thor_amd
+    O = build_oracle_c()
+    rng = np.random.default_rng(900 + bd)
+    peak = (1 << bd) - 1
+    for size in (4, 8, 16, 32, 64):
+        n = 8
+        org = rng.integers(0, peak + 1, size=(n, size, size), dtype=np.uint16)
+        pred = rng.integers(0, peak + 1, size=(n, size, size), dtype=np.uint16)
+        org[0] = peak; pred[0] = 0
+        org[1] = 0; pred[1] = peak
+        org[2] = pred[2]
+        org[3] = (np.indices((size, size)).sum(0) % 2 * peak).astype(np.uint16); pred[3] = peak - org[3]
+        for qp, ctype in ((8, 0), (30, 2), (51, 1)):
+            coefq, rec, cbp = thor_amd.code_tu_batch(org, pred, qp, ctype, 0, bitdepth=bd)
+            q = min(size, 16)
+            for i in range(n):
+                cq = np.zeros((q, q), dtype=np.int16); rc = np.zeros((size, size), dtype=np.uint16)
+                c = O.orc_code_tu16(vp(np.ascontiguousarray(org[i])), vp(np.ascontiguousarray(pred[i])), size, qp, ctype, 0, vp(cq), vp(rc), bd)
+                assert c == cbp[i] and (cq == coefq[i]).all() and (rc == rec[i]).all(), (bd, size, qp, i)
+
+
+@pytest.mark.parametrize('bd', [10, 12])
 def test_deblock_frame_hbd_matches_reference_kat(bd):
     K4 = K4S[bd]
     import thor_amd
@@ -399,3 +424,66 @@ def test_engine_only_overflow_keeps_position_and_canaries():
     import thor_amd
     import kat_bits as B
     B.check_overflow(lambda par, coef, b1, bt: thor_amd.binding.kat_coeff_syntax(par, coef, B.CO_WORDS, b1, bt))
+
+
+# ---- the layer between the sample kernels and the stream on the device: the neighbour context of a coding block (tk_block_ctx.h) and the block cost (tk_block_rd.h:
+# ssd_part, ssd_total, rd_cost) against the reference's own answers (tests/golden/gen_kat11.py -> kat11.npz), one launch per call --------------------------------
+def test_block_context_matches_reference_kat():
+    """upright_avail, downleft_avail, get_mv_pred, get_mv_cands and find_contexts on the device, one wavefront per item, at EVERY block position of three frames
+    whose sizes are no multiples of the superblock (200x136, 328x264, 264x40), superblocks of 64 and 128, sizes 8..128, on random cell grids with areas of equal
+    predictions: bit-exact against get_mv_pred_lbd, get_mv_skip_lbd and get_mv_merge_lbd (the generator asserts that the two return the same on every item, so
+    the one recorded answer is both call sites'), find_block_contexts_lbd with enable 0 / 1 and the two availability functions."""
+    import thor_amd
+    from kat_block import K11, ctx_report
+    total = 0
+    for fi in range(3):
+        par, want = K11[f'ctx{fi}_par'].astype(np.int32), K11[f'ctx{fi}_out'].astype(np.int32)
+        got = thor_amd.binding.kat_block_ctx(K11[f'ctx{fi}_cells'], int(par[0][3]) // 4, par)
+        rep = ctx_report(got, want, par)
+        assert rep is None, f'frame {fi}: {rep}'
+        total += len(par)
+    assert total >= 5000
+
+
+@pytest.mark.parametrize('bd', [8, 10, 12])
+def test_block_cost_matches_reference_kat(bd):
+    """ssd_total(ssd_part()) of the luma plane - the SP_GLOBAL instance on an original with the item's byte skew and stride (the 16 / 8 / 4 byte row loops on
+    v_dot4 / v_dot2 and the per-sample loops, power-of-two and other widths), the SP_LDS instance for blocks up to the size the build keeps in LDS - against a numpy int64 sum, and rd_cost
+    (three planes, 64-lane reduction, rate term, 2^30 clamp; with and without the luma SSD passed in) against the reference's cost_calc: sizes 8..128, frame-edge
+    rectangles, all-max against all-zero 128x128 blocks (8 bit: 1.6e9, the 32-bit headroom; 12 bit: 4e11, the 64-bit reduction), costs at and within 1000 below
+    the clamp.  No tolerance."""
+    import thor_amd
+    from kat_block import K11, cost_want, cost_report
+    par, lam = K11[f'cost{bd}_par'], K11[f'cost{bd}_lam']
+    assert len(par) >= 90
+    got = thor_amd.binding.kat_block_cost(par, lam, K11[f'cost{bd}_org'], K11[f'cost{bd}_rec'], bd)
+    rep = cost_report(got, cost_want(bd, thor_amd.binding.kat_lds_block()), par, lam)
+    assert rep is None, rep
+
+
+@pytest.mark.parametrize('bd', [8, 10])
+def test_intra_sad_search_matches_reference_kat(bd):
+    """intra_sad_search on the device, one wavefront per item and one launch, against the reference's search_intra_prediction_params: mode and SAD (shifted by
+    bitdepth - 8), bit-exact.  A 96x80 reconstructed plane; sizes 8 / 16 / 32 at the frame corner, in the top row, the left column and inside with and without
+    up-right / down-left (from the position; superblocks 64 and 128); 4 and 10 modes; random originals, originals equal or close to one mode's prediction (each
+    of the ten modes wins), flat blocks on the flat part of the plane, where every mode ties and the first in evaluation order must win."""
+    import thor_amd
+    from kat_block import K11, intra_report
+    par = K11[f'intra{bd}_par']
+    assert len(par) >= 300
+    got = thor_amd.binding.kat_intra_search(par, K11[f'intra{bd}_plane'], K11[f'intra{bd}_org'], bd)
+    rep = intra_report(got, K11[f'intra{bd}_out'], par)
+    assert rep is None, rep
+
+
+@pytest.mark.parametrize('bd', [8, 10, 12])
+def test_build_org8_matches_numpy(bd):
+    """build_org8 (the saturated 2 * org - pred of a bi-prediction search step) on the device against numpy: sizes 8..64, the four-sample path and the per-sample
+    path (originals skewed by 2 bytes, strides that break the alignment), the global-memory instance and - for blocks the build keeps in LDS - the LDS instance;
+    every block saturates at both ends; samples outside the items' blocks stay untouched."""
+    import thor_amd
+    from kat_block import org8_items, org8_report
+    par, org, pred = org8_items(bd)
+    og, ol = thor_amd.binding.kat_build_org8(par, org, pred, bd, fill=5)
+    rep = org8_report(bd, par, org, pred, og, ol, thor_amd.binding.kat_lds_block(), 5)
+    assert rep is None, rep

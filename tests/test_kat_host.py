@@ -1,7 +1,8 @@
 """Round 6: the known answers of tests/golden/kat5.npz (recorded from the reference functions, tests/golden/gen_kat5.py) against the 1-lane HOST build of the
 device functions (tests/hostsim/kat_host.cpp: make_edges + pred_intra, the two CLPF passes, cdef_find_dir, cdef_filter_px) - the CPU twin of the
 device known-answer tests (tests/test_gpu_kat.py), bitdepth 8 / 10 / 12.  The motion search: the known answers of tests/golden/kat8.npz (the reference's
-motion_estimate / motion_estimate_bi, tests/golden/gen_kat8.py) against the host build of tk_me.h (tests/hostsim/kat_host_me.cpp), 1-lane and 64-lane teams."""
+motion_estimate / motion_estimate_bi, tests/golden/gen_kat8.py) against the host build of tk_me.h (tests/hostsim/kat_host_me.cpp), 1-lane and 64-lane teams.
+The neighbour context of a coding block and the block cost: kat11.npz (tests/golden/gen_kat11.py) against tests/hostsim/kat_host_ctx.cpp, 1-lane and 8-lane teams."""
 import ctypes as C
 import os
 import subprocess
@@ -255,3 +256,93 @@ def test_block_syntax_engine_only_long_codewords_and_overflow_host_build(tmp_pat
         return out, b1, bt
     B.check_long_codewords(run)
     B.check_overflow(run)
+
+
+# ---- the neighbour context of a coding block and the block cost (thor_amd/csrc/tk_block_ctx.h, tk_block_rd.h) against the reference (tests/golden/gen_kat11.py) -----
+def build_ctx_host(d, lanes):
+    so = str(d / ('kat_host_ctx_l.so' if lanes else 'kat_host_ctx.so'))
+    extra = ['-O2', '-DTHOR_HOSTSIM_LANES=64', '-pthread'] if lanes else ['-O1']
+    subprocess.check_call(['g++', '-std=c++17', '-fno-strict-aliasing', '-DTHOR_HOSTSIM', '-ffp-contract=off', '-shared', '-fPIC'] + extra + ['-o', so,
+                           os.path.join(ROOT, 'tests', 'hostsim', 'kat_host_ctx.cpp')])
+    lib = C.CDLL(so)
+    lib.h_block_ctx.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.h_block_cost.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
+    lib.h_intra_search.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
+    lib.h_build_org8.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
+    return lib
+
+
+def intra_host(lib, bd, lanes):
+    from kat_block import K11, intra_report
+    par, plane, org = (np.ascontiguousarray(K11[f'intra{bd}_{k}']) for k in ('par', 'plane', 'org'))
+    got = np.full((len(par), 2), -77, dtype=np.int32)
+    assert lib.h_intra_search(lanes, len(par), P(par), P(plane), plane.shape[1], plane.shape[0], P(org), len(org), bd, P(got)) == 0
+    assert len(par) >= 300
+    return intra_report(got, K11[f'intra{bd}_out'], par)
+
+
+def org8_host(lib, bd, lanes):
+    from kat_block import org8_items, org8_report
+    par, org, pred = org8_items(bd)
+    fill = 5
+    og, ol = np.full(len(org), fill, org.dtype), np.full(len(org), fill, org.dtype)
+    assert lib.h_build_org8(lanes, len(par), P(par), P(org), P(pred), len(org), bd, P(og), P(ol)) == 0
+    return org8_report(bd, par, org, pred, og, ol, lib.h_lds_block(), fill)
+
+
+def cost_host(lib, bd, lanes):
+    from kat_block import K11
+    par, lam = np.ascontiguousarray(K11[f'cost{bd}_par']), np.ascontiguousarray(K11[f'cost{bd}_lam'])
+    org, rec = np.ascontiguousarray(K11[f'cost{bd}_org']), np.ascontiguousarray(K11[f'cost{bd}_rec'])
+    got = np.zeros((len(par), 4), dtype=np.uint64)
+    assert lib.h_block_cost(lanes, len(par), P(par), P(lam), P(org), P(rec), len(org), bd, P(got)) == 0
+    return got, par, lam
+
+
+def test_block_context_and_cost_host_build_match_reference_kat(tmp_path):
+    """Every item of kat11.npz with 1-lane teams.  Context: every block position of three frames (200x136, 328x264, 264x40: blocks over the right and bottom
+    edges), superblocks of 64 and 128, sizes 8..128 - get_mv_pred, the count and both candidates of get_mv_cands (= the reference's get_mv_skip and get_mv_merge),
+    find_contexts with enable 0 / 1 and the two availability flags, bit-exact.  Cost: ssd_part + ssd_total against a numpy int64 sum and rd_cost against the
+    reference's cost_calc at bitdepth 8 / 10 / 12 - every alignment path of the original (16 / 8 / 4 bytes, per sample), frame-edge rectangles, all-max blocks, the
+    2^30 clamp."""
+    from kat_block import K11, ctx_report, cost_want, cost_report
+    L1 = build_ctx_host(tmp_path, 0)
+    total = 0
+    for fi in range(3):
+        cells, par, want = np.ascontiguousarray(K11[f'ctx{fi}_cells']), np.ascontiguousarray(K11[f'ctx{fi}_par'].astype(np.int32)), K11[f'ctx{fi}_out'].astype(np.int32)
+        got = np.full(want.shape, -77, dtype=np.int32)
+        assert L1.h_block_ctx(P(cells), len(cells), int(par[0][3]) // 4, len(par), P(par), P(got)) == 0
+        rep = ctx_report(got, want, par)
+        assert rep is None, f'frame {fi}: {rep}'
+        total += len(par)
+    assert total >= 5000
+    for bd in (8, 10, 12):
+        got, par, lam = cost_host(L1, bd, 1)
+        assert len(par) >= 90
+        rep = cost_report(got, cost_want(bd, L1.h_lds_block()), par, lam)
+        assert rep is None, f'bitdepth {bd}: {rep}'
+
+
+def test_block_cost_host_8_lane_team_matches_reference_kat(tmp_path):
+    """The cost family with teams of 8 OS threads: the lane-strided row loops of ssd_part and the cross-lane sums (team_sum, team_sum64) of ssd_total."""
+    from kat_block import cost_want, cost_report
+    L8 = build_ctx_host(tmp_path, 1)
+    for bd in (8, 10, 12):
+        got, par, lam = cost_host(L8, bd, 8)
+        rep = cost_report(got, cost_want(bd, L8.h_lds_block()), par, lam)
+        assert rep is None, f'bitdepth {bd}, 8 lanes: {rep}'
+
+
+def test_intra_sad_search_and_build_org8_host_build_match_reference_kat(tmp_path):
+    """intra_sad_search (tk_block_search.h) with 1-lane and 8-lane teams against the reference's search_intra_prediction_params at bitdepth 8 and 10: mode and
+    SAD of every item of kat11.npz - sizes 8 / 16 / 32 at the frame corner, in the top row, the left column and inside with every up-right / down-left
+    availability (superblocks 64 and 128), 4 and 10 modes, random originals, originals equal or close to one mode's prediction, flat blocks on a flat plane
+    (every mode ties; the first one weighed wins).  build_org8 against clip(2 * org - pred) at bitdepth 8 / 10 / 12, aligned and skewed originals."""
+    L1, L8 = build_ctx_host(tmp_path, 0), build_ctx_host(tmp_path, 1)
+    for lib, lanes in ((L1, 1), (L8, 8)):
+        for bd in (8, 10):
+            rep = intra_host(lib, bd, lanes)
+            assert rep is None, f'bitdepth {bd}, {lanes} lanes: {rep}'
+        for bd in (8, 10, 12):
+            rep = org8_host(lib, bd, lanes)
+            assert rep is None, f'bitdepth {bd}, {lanes} lanes: {rep}'

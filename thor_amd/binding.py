@@ -656,6 +656,60 @@ def kat_early_skip(chroma, org, pred, size, qp, thr, bitdepth=8):
     return out
 
 
+def kat_block_ctx(cells, cell_stride, par):
+    """thor_hip_kat_block_ctx: cells (ncells, 16) bytes = thor_hip_cell records in raster order; par (n, 6) ypos, xpos, size, frame width, frame height,
+    superblock size.  Returns (n, 23): get_mv_pred, the candidates of get_mv_cands, the contexts with enable 0 / 1, the two availability flags."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint8); par = np.ascontiguousarray(par, dtype=np.int32)
+    assert cells.ndim == 2 and cells.shape[1] == 16 and par.ndim == 2 and par.shape[1] == 6
+    out = np.full((len(par), 23), -77, dtype=np.int32)
+    _kat('thor_hip_kat_block_ctx', _vp(cells), C.c_longlong(len(cells)), cell_stride, len(par), _vp(par), _vp(out))
+    return out
+
+
+def kat_lds_block():
+    """thor_hip_kat_lds_block: the largest coding-block size the build keeps in LDS."""
+    fn = lib().thor_hip_kat_lds_block
+    fn.restype = C.c_int
+    return fn()
+
+
+def kat_block_cost(par, lam, org, rec, bitdepth=8):
+    """thor_hip_kat_block_cost: par (n, 7) size, bw, bh, nbits, off, skew, stride; lam (n,); org / rec: sample pools holding the compact 4:2:0 blocks at `off`.
+    Returns (n, 4) uint64: luma SSD (global-memory instance), luma SSD (LDS instance, all ones for blocks the engine keeps in global memory), rd_cost,
+    rd_cost with the luma SSD passed in."""
+    T = _pix(bitdepth)
+    org = np.ascontiguousarray(org, dtype=T).ravel(); rec = np.ascontiguousarray(rec, dtype=T).ravel()
+    par = np.ascontiguousarray(par, dtype=np.int32); lam = np.ascontiguousarray(lam, dtype=np.float64)
+    assert par.ndim == 2 and par.shape[1] == 7 and len(lam) == len(par) and len(org) == len(rec)
+    out = np.zeros((len(par), 4), dtype=np.uint64)
+    _kat('thor_hip_kat_block_cost', len(par), _vp(par), _vp(lam), _vp(org), _vp(rec), C.c_longlong(len(org)), bitdepth, _vp(out))
+    return out
+
+
+def kat_intra_search(par, plane, org, bitdepth=8):
+    """thor_hip_kat_intra_search: par (n, 6) ypos, xpos, size, superblock size, num_intra_modes, off; plane (height, width) reconstructed luma; org: pool of
+    compact original blocks.  Returns (n, 2): intra mode, SAD."""
+    T = _pix(bitdepth)
+    plane = np.ascontiguousarray(plane, dtype=T); org = np.ascontiguousarray(org, dtype=T).ravel()
+    par = np.ascontiguousarray(par, dtype=np.int32)
+    assert plane.ndim == 2 and par.ndim == 2 and par.shape[1] == 6
+    out = np.full((len(par), 2), -77, dtype=np.int32)
+    _kat('thor_hip_kat_intra_search', len(par), _vp(par), _vp(plane), plane.shape[1], plane.shape[0], _vp(org), C.c_longlong(len(org)), bitdepth, _vp(out))
+    return out
+
+
+def kat_build_org8(par, org, pred, bitdepth=8, fill=0):
+    """thor_hip_kat_build_org8: par (n, 4) size, off, skew, stride; org / pred: sample pools.  Returns (out_global, out_lds): pools pre-filled with `fill` holding
+    each item's result at `off` (out_lds only for blocks the engine keeps in LDS)."""
+    T = _pix(bitdepth)
+    org = np.ascontiguousarray(org, dtype=T).ravel(); pred = np.ascontiguousarray(pred, dtype=T).ravel()
+    par = np.ascontiguousarray(par, dtype=np.int32)
+    assert par.ndim == 2 and par.shape[1] == 4 and len(org) == len(pred)
+    og = np.full(len(org), fill, dtype=T); ol = np.full(len(org), fill, dtype=T)
+    _kat('thor_hip_kat_build_org8', len(par), _vp(par), _vp(org), _vp(pred), C.c_longlong(len(org)), bitdepth, _vp(og), _vp(ol))
+    return og, ol
+
+
 def kat_coeff_syntax(par, coef, words, buf_single, buf_team):
     """thor_hip_kat_coeff_syntax: par (n, 4) size, type, start bit, capacity; coef (n, 256); buf_* (n, words) uint32, pre-filled.  Returns (out (n, 6),
     buf_single, buf_team) - the buffers as the device left them."""

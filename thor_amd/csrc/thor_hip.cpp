@@ -64,3 +64,4 @@ __device__ Tables g_tab;
 #include "hip_abi_seq.h"
 #include "hip_abi_seam.h"
 #include "hip_kat.h"
+#include "hip_kat_block.h"
