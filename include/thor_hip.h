@@ -235,6 +235,53 @@ size_t thor_hip_rgb_bytes_for(int width, int height, const thor_hip_rgb_format* 
 int thor_hip_stage_frame_rgb(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_rgb_format* fmt, int on_device);
 int thor_hip_get_recon_rgb(thor_hip_encoder* e, int stream, void* frame, const thor_hip_rgb_format* fmt, int on_device);
 
+/* Frames of another size: staging resamples them to the encoder's width x height on the device (k_scale_in), so that one decoder surface can feed
+ * engines at several sizes and a source whose size is no multiple of 8 can be coded at the nearest legal size.  Staging a scaled frame means exactly:
+ * (1) resample the source - a 4:2:0 frame of input_bitdepth samples, src_width x src_height, in `layout` at the SOURCE size - to a planar 4:2:0 frame
+ * of input_bitdepth samples at width x height (below), and (2) stage that frame, so every sample is then widened by bitdepth - input_bitdepth like
+ * any staged frame.  Integers only; nothing of it is floating point, on the host or on the device.
+ *
+ * Each plane is resampled separably, horizontally first, then vertically.  Luma: S -> T is src_width -> width and src_height -> height; chroma:
+ * src_width / 2 -> width / 2 and src_height / 2 -> height / 2.
+ * Taps.  For one axis with source length S, destination length T, D = 2 * max(S, T) and destination index i, the distance numerator of source
+ * sample k is
+ *   centre-aligned: n(k) = (2i + 1) * S - (2k + 1) * T          co-sited: n(k) = 2 * (i * S - k * T)
+ * Co-sited is used only for the horizontal axis of chroma when chroma_site == 1 (left, the MPEG-2 / H.264 default, as in thor_hip_rgb_format);
+ * everything else is centre-aligned.  The filter argument is n / D: the support stretches with the ratio when downscaling (which anti-aliases) and is
+ * one source sample wide when upscaling.  The taps are all k with a = |n(k)| < A * D, a contiguous range.  Weights, in exact 64-bit integers:
+ *   THOR_HIP_SCALE_BILINEAR (A = 1): W = D - a
+ *   THOR_HIP_SCALE_BICUBIC (Catmull-Rom, A = 2): a < D: W = 3a^3 - 5a^2 D + 2D^3;  otherwise W = -a^3 + 5a^2 D - 8a D^2 + 4D^3
+ * Coefficients: c(k) = floor((2 * W(k) * 16384 + sumW) / (2 * sumW)), sumW the sum over the taps (floor, not truncation: W can be negative); then
+ * 16384 - sum c is added to the tap with the largest W, the lowest k among equals, so every tap set sums to 16384 exactly.  A tap outside
+ * [0, S - 1] reads the edge sample.  S == T gives the single tap 16384 at k = i: a scaled call at the coded size is layout staging, exactly.
+ * Passes, with g = 2 guard bits, n = input_bitdepth and x = s >> msb as in layout staging:
+ *   horizontal: I = (sum c(k) * x(k) + (1 << (13 - g))) >> (14 - g)          (arithmetic shift; I is signed)
+ *   vertical:   O = clamp((sum c(k) * I(k) + (1 << (13 + g))) >> (14 + g), 0, 2^n - 1)
+ * Limits, refused before the device is touched: src_width and src_height even and within 16 .. 8192; on each axis S <= 8 * T and T <= 8 * S (at most
+ * 33 taps); an unknown filter or site; a layout that is refused at the source size; and, when a table is built, a tap set with sum |c| > 26214
+ * (with that bound I fits 16 bits and the vertical sum 32 bits at n = 12).  RGB sources are not scaled.  There is no scaled fetch: reconstruction and
+ * PSNR are at the coded size, against the staged (scaled) original. */
+enum { THOR_HIP_SCALE_BILINEAR = 0, THOR_HIP_SCALE_BICUBIC = 1 };
+typedef struct thor_hip_scale {
+  int size;         /* sizeof(thor_hip_scale) */
+  int src_width;    /* of the frame handed over */
+  int src_height;
+  int filter;       /* THOR_HIP_SCALE_* */
+  int chroma_site;  /* 0: centre, 1: left - the horizontal position of the chroma samples, in the source and in the result */
+} thor_hip_scale;
+/* Bytes the source frame spans from its base in `layout` (NULL = packed planar) at the source size; 0 = refused (see the limits above; a table is not
+ * built).  thor_hip_scale_bytes_for needs no encoder and no device. */
+size_t thor_hip_scale_bytes(const thor_hip_encoder* e, const thor_hip_scale* scale, const thor_hip_frame_layout* layout);
+size_t thor_hip_scale_bytes_for(int width, int height, int input_bitdepth, const thor_hip_scale* scale, const thor_hip_frame_layout* layout);
+/* thor_hip_stage_frame_layout for a frame of another size: same return values (0; 1 for a bad argument, a refused scale or layout or a base pointer
+ * that is not sample-aligned - found before the device is touched, and the slot stays as it was), same ordering, synchronous at return.  The encoder
+ * keeps the tap tables of the most recent (source size, filter, site) and rebuilds them only when those change. */
+int thor_hip_stage_frame_scaled(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_scale* scale,
+                                const thor_hip_frame_layout* layout /* at the SOURCE size; NULL = packed planar */, int on_device);
+/* No device: the taps of destination index i on one axis (S -> T).  *first = the first source index (negative at the left edge), coeff[0 .. count - 1]
+ * the coefficients.  Returns the count; 0 = refused (S or T outside 1 .. 8192, ratio above 8, unknown filter, i outside [0, T), cap too small). */
+int thor_hip_scale_taps(int S, int T, int filter, int cosited, int i, int* first, short* coeff, int cap);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -444,6 +491,10 @@ int thor_hip_frame_sse_depth(const void* a, const void* b, int w, int h, int bit
  * Returns 0, 1 = bad argument or refused layout (before the device is touched), 3 = no device. */
 int thor_hip_kat_layout_in(const void* src, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* planar_out);
 int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth, void* dst);
+/* k_scale_in on host buffers without an encoder: `src` holds thor_hip_scale_bytes_for(w, h, input_bitdepth, scale, layout) bytes; planar_out receives
+ * the packed planar w x h frame at `bitdepth`.  Same return values. */
+int thor_hip_kat_scale_in(const void* src, const thor_hip_scale* scale, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth,
+                          void* planar_out);
 /* The same for k_rgb_in / k_rgb_out: `src` / `dst` hold thor_hip_rgb_bytes_for(w, h, fmt) bytes in `fmt` (dst: plus 64 guard bytes, all of it uploaded
  * before the kernel runs and downloaded afterwards); the planar frames are at `bitdepth` (k_rgb_out rounds back to input_bitdepth first).  Any depth
  * of `fmt` goes with any input_bitdepth <= bitdepth.  Same return values. */

@@ -136,6 +136,18 @@ class RgbFormat(C.Structure):
         return cls(RGB_PLANAR, depth, msb_aligned, matrix, full_range, chroma_site, pitch, plane_stride)
 
 
+SCALE_BILINEAR, SCALE_BICUBIC = 0, 1   # THOR_HIP_SCALE_*
+
+
+class Scale(C.Structure):
+    """thor_hip_scale (include/thor_hip.h): the size of the frames handed over, the resampling filter and the horizontal position of the chroma
+    samples (0 centre, 1 left).  Staging such a frame resamples it to the encoder's size on the device."""
+    _fields_ = [('size', C.c_int), ('src_width', C.c_int), ('src_height', C.c_int), ('filter', C.c_int), ('chroma_site', C.c_int)]
+
+    def __init__(self, src_width=0, src_height=0, filter=SCALE_BICUBIC, chroma_site=1):
+        super().__init__(C.sizeof(Scale), src_width, src_height, filter, chroma_site)
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -194,6 +206,14 @@ def lib():
         L.thor_hip_get_recon_rgb.argtypes = [C.c_void_p, C.c_int, C.c_void_p, RP, C.c_int]
         L.thor_hip_kat_rgb_in.argtypes = [C.c_void_p, RP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_kat_rgb_out.argtypes = [C.c_void_p, RP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        SP = C.POINTER(Scale)
+        L.thor_hip_scale_bytes.restype = C.c_size_t
+        L.thor_hip_scale_bytes.argtypes = [C.c_void_p, SP, LP]
+        L.thor_hip_scale_bytes_for.restype = C.c_size_t
+        L.thor_hip_scale_bytes_for.argtypes = [C.c_int, C.c_int, C.c_int, SP, LP]
+        L.thor_hip_stage_frame_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, SP, LP, C.c_int]
+        L.thor_hip_scale_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_short), C.c_int]
+        L.thor_hip_kat_scale_in.argtypes = [C.c_void_p, SP, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -304,6 +324,27 @@ class Encoder:
         rc = lib().thor_hip_get_recon_rgb(self.h, stream, C.c_void_p(dev_ptr), C.byref(fmt), 1)
         if rc:
             raise RuntimeError(f'thor_hip_get_recon_rgb rc={rc}')
+
+    def scale_bytes(self, scale, layout=None):
+        """Bytes a source frame of `scale` (a Scale) spans in `layout` (a FrameLayout at the source size; None: packed planar); raises if refused."""
+        n = lib().thor_hip_scale_bytes(self.h, C.byref(scale), C.byref(layout) if layout is not None else None)
+        if not n:
+            raise ValueError('scaled staging refused (odd or out-of-range source size, ratio above 8, unknown filter or site, layout refused at the source size)')
+        return n
+
+    def stage_scaled(self, stream, slot, array, scale, layout=None):
+        """Stage a host frame of another size (scale_bytes(scale, layout) bytes): resampled to the encoder's size on the device, then staged."""
+        frame = np.ascontiguousarray(array).view(np.uint8).reshape(-1)
+        assert frame.size >= self.scale_bytes(scale, layout)
+        rc = lib().thor_hip_stage_frame_scaled(self.h, stream, slot, frame.ctypes.data_as(C.c_void_p), C.byref(scale), C.byref(layout) if layout is not None else None, 0)
+        if rc:
+            raise RuntimeError(f'thor_hip_stage_frame_scaled rc={rc}')
+
+    def stage_scaled_device(self, stream, slot, dev_ptr, scale, layout=None):
+        """The same for a frame that lives in HBM (e.g. tensor.data_ptr()), read in place by the kernel that writes the slot."""
+        rc = lib().thor_hip_stage_frame_scaled(self.h, stream, slot, C.c_void_p(dev_ptr), C.byref(scale), C.byref(layout) if layout is not None else None, 1)
+        if rc:
+            raise RuntimeError(f'thor_hip_stage_frame_scaled rc={rc}')
 
     def begin_sequence(self, stream, skip, num_frames, file_frames):
         """Fix the chunk [skip, skip+num_frames) of a file_frames-long input (thor_hip_begin_sequence)."""
@@ -832,3 +873,24 @@ def kat_rgb_out(planar, fmt, width, height, input_bitdepth, bitdepth, dst):
     assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.size == rgb_bytes(fmt, width, height) + 64 > 64
     _kat('thor_hip_kat_rgb_out', _vp(a), C.byref(fmt), width, height, input_bitdepth, bitdepth, _vp(dst))
     return dst
+
+
+def scale_bytes(scale, width, height, input_bitdepth=8, layout=None):
+    """thor_hip_scale_bytes_for: bytes the source frame of `scale` spans when it feeds a width x height encoder, 0 if refused.  Needs no device."""
+    return lib().thor_hip_scale_bytes_for(width, height, input_bitdepth, C.byref(scale), C.byref(layout) if layout is not None else None)
+
+
+def scale_taps(S, T, filter, cosited, i):
+    """thor_hip_scale_taps: (first source index, [coefficients]) of destination index i on an axis S -> T; None if refused.  Needs no device."""
+    first, coef = C.c_int(0), (C.c_short * 33)()
+    n = lib().thor_hip_scale_taps(S, T, filter, cosited, i, C.byref(first), coef, 33)
+    return (first.value, list(coef[:n])) if n else None
+
+
+def kat_scale_in(src, scale, width, height, input_bitdepth, bitdepth, layout=None):
+    """thor_hip_kat_scale_in: a source frame (a uint8 array of at least scale_bytes; its address decides the kernel's path) through k_scale_in ->
+    packed planar 4:2:0 of width x height at `bitdepth`."""
+    assert src.dtype == np.uint8 and src.flags.c_contiguous and src.size >= scale_bytes(scale, width, height, input_bitdepth, layout) > 0
+    out = np.zeros(width * height * 3 // 2, dtype=_pix(bitdepth))
+    _kat('thor_hip_kat_scale_in', _vp(src), C.byref(scale), C.byref(layout) if layout is not None else None, width, height, input_bitdepth, bitdepth, _vp(out))
+    return out

@@ -114,7 +114,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given) return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given) return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -401,6 +401,55 @@ int thor_hip_get_recon_rgb(thor_hip_encoder* e, int stream, void* frame, const t
       HIPCHECK(hipStreamSynchronize(g_stream));
     } else
       E.eng.fetch_rgb_host(E.eng.st[stream].rec.p, frame, R);
+  });
+  return 0;
+}
+// ---- frames of another size: tk_scale.h ScalePlan, k_scale_in ----
+// The caller's two structures against a width x height engine; false: refused (a wrong `size` included).  Touches no device, builds no table.
+static bool scale_args_resolved(const thor_hip_scale* sc, const thor_hip_frame_layout* l, int width, int height, int input_bitdepth, PixLayout& L) {
+  static const thor_hip_frame_layout packed = {sizeof(thor_hip_frame_layout), THOR_HIP_CHROMA_PLANAR, 0, 0, 0, 0, 0};
+  if (!sc || sc->size != (int)sizeof(thor_hip_scale)) return false;
+  if (!l) l = &packed;
+  if (l->size != (int)sizeof(thor_hip_frame_layout)) return false;
+  return resolve_scale_args(sc->src_width, sc->src_height, sc->filter, sc->chroma_site, l->chroma, l->msb_aligned, l->pitch_y, l->pitch_c, l->offset_u, l->offset_v,
+                            width, height, input_bitdepth, L);
+}
+size_t thor_hip_scale_bytes_for(int width, int height, int input_bitdepth, const thor_hip_scale* scale, const thor_hip_frame_layout* layout) {
+  PixLayout L;
+  return scale_args_resolved(scale, layout, width, height, input_bitdepth, L) ? L.bytes : 0;
+}
+size_t thor_hip_scale_bytes(const thor_hip_encoder* e, const thor_hip_scale* scale, const thor_hip_frame_layout* layout) {
+  return e ? thor_hip_scale_bytes_for(e->sp.width, e->sp.height, e->sp.input_bitdepth, scale, layout) : 0;
+}
+int thor_hip_scale_taps(int S, int T, int filter, int cosited, int i, int* first, short* coeff, int cap) {
+  int16_t c[SCALE_MAX_TAPS];
+  int f = 0;
+  if (!first || !coeff || cap < 1) return 0;
+  const int n = scale_taps(S, T, filter, cosited, i, &f, c, cap < SCALE_MAX_TAPS ? cap : SCALE_MAX_TAPS);
+  for (int j = 0; j < n; j++) coeff[j] = c[j];
+  if (n) *first = f;
+  return n;
+}
+int thor_hip_stage_frame_scaled(thor_hip_encoder* e, int stream, int slot, const void* frame, const thor_hip_scale* scale, const thor_hip_frame_layout* layout,
+                                int on_device) {
+  PixLayout L;
+  if (!e || stream < 0 || stream >= e->S || slot < 0 || !frame) return 1;
+  if (!scale_args_resolved(scale, layout, e->sp.width, e->sp.height, e->sp.input_bitdepth, L) || (uintptr_t)frame % (e->sp.input_bitdepth > 8 ? 2 : 1)) return 1;
+  static const thor_hip_frame_layout packed = {sizeof(thor_hip_frame_layout), THOR_HIP_CHROMA_PLANAR, 0, 0, 0, 0, 0};
+  const thor_hip_frame_layout* l = layout ? layout : &packed;
+  ENC_DISPATCH(e, {
+    // the tap tables: kept from the last call with this geometry, else built now - still before the device is touched
+    if (!E.eng.resolve_scaled(scale->src_width, scale->src_height, scale->filter, scale->chroma_site, l->chroma, l->msb_aligned, l->pitch_y, l->pitch_c,
+                              l->offset_u, l->offset_v))
+      return 1;
+    auto& v = E.staged[stream];
+    if ((int)v.size() <= slot) v.resize(slot + 1);
+    if (!v[slot].base_y) v[slot].alloc(e->sp.width, e->sp.height, 0);
+    if (on_device) {  // the kernel reads the caller's buffer and writes the slot
+      E.eng.scale_in(frame, v[slot].p);
+      HIPCHECK(hipStreamSynchronize(g_stream));
+    } else
+      E.eng.stage_scaled_host(frame, v[slot].p);
   });
   return 0;
 }

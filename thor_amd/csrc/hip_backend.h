@@ -389,6 +389,22 @@ template void launch_rgb_in<uint16_t>(const void*, const RgbFormat&, const Plane
 template void launch_rgb_out<uint8_t>(const Plane3<uint8_t>&, void*, const RgbFormat&, int, int, int, int);
 template void launch_rgb_out<uint16_t>(const Plane3<uint16_t>&, void*, const RgbFormat&, int, int, int, int);
 
+// A frame of another size -> the engine's planes, on g_stream (tk_encoder.h declares it).  `frame`: device memory in layout L at the source size;
+// `tab`: the plan's tables in device memory; `vrows`: the most source rows one tile reaches (ScaleAxisTable::span of the two vertical tables).
+template <typename PIX> void launch_scale_in(const void* frame, const PixLayout& L, const ScaleTables& tab, int vrows, const Plane3<PIX>& dst, int src_w, int width,
+                                             int height, int bitdepth, int input_bitdepth) {
+  const int up = bitdepth - input_bitdepth, maxv = (1 << input_bitdepth) - 1;
+  const dim3 grid(scale_items(width, height));
+  const size_t lds = (size_t)vrows * SCALE_TW * sizeof(int16_t);
+  if (vrows < 1 || vrows > SCALE_VROWS) { fprintf(stderr, "launch_scale_in: %d intermediate rows\n", vrows); abort(); }
+  if constexpr (sizeof(PIX) == 1) hipLaunchKernelGGL((k_scale_in<uint8_t, uint8_t>), grid, dim3(256), lds, g_stream, frame, L, tab, dst, src_w, width, height, maxv, up);
+  else if (input_bitdepth == 8) hipLaunchKernelGGL((k_scale_in<uint8_t, uint16_t>), grid, dim3(256), lds, g_stream, frame, L, tab, dst, src_w, width, height, maxv, up);
+  else hipLaunchKernelGGL((k_scale_in<uint16_t, uint16_t>), grid, dim3(256), lds, g_stream, frame, L, tab, dst, src_w, width, height, maxv, up);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_scale_in<uint8_t>(const void*, const PixLayout&, const ScaleTables&, int, const Plane3<uint8_t>&, int, int, int, int, int);
+template void launch_scale_in<uint16_t>(const void*, const PixLayout&, const ScaleTables&, int, const Plane3<uint16_t>&, int, int, int, int, int);
+
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {
 // Owning device array of n elements, zeroed (dev_alloc clears), filled from `h` when given; freed with its scope.

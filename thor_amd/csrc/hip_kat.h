@@ -778,6 +778,40 @@ extern "C" int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_fra
   else kat_layout_out<uint16_t>((const uint16_t*)planar_in, L, w, h, input_bitdepth, bitdepth, dst);
   return 0;
 }
+// k_scale_in on a host buffer, like thor_hip_kat_layout_in: `src` is a frame in `layout` (NULL = packed planar) at the source size; the device copy keeps
+// the host pointer's offset from a 16-byte boundary.
+template <typename PIX> static void kat_scale_in(const void* src, const ScalePlan& P, int w, int h, int input_bitdepth, int bitdepth, PIX* out) {
+  const size_t skew = (uintptr_t)src & 15;
+  DevBuf<uint8_t> d(P.L.bytes + 16);
+  backend::h2d(d.p + skew, src, P.L.bytes);
+  std::vector<uint8_t> hb(P.blob_bytes());
+  DevBuf<uint8_t> tb(hb.size());
+  const ScaleTables tab = P.pack(hb.data(), tb.p);
+  backend::h2d(tb.p, hb.data(), hb.size());
+  DevFrame<PIX> f;
+  f.alloc(w, h, 0);
+  launch_scale_in<PIX>(d.p + skew, P.L, tab, P.t[1].span > P.t[3].span ? P.t[1].span : P.t[3].span, f.p, P.src_w, w, h, bitdepth, input_bitdepth);
+  backend::dev_sync();
+  download_yuv(f, out, w, h);
+  f.release();
+}
+extern "C" int thor_hip_kat_scale_in(const void* src, const thor_hip_scale* scale, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth,
+                                     void* planar_out) {
+  auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };
+  PixLayout L;
+  if (!src || !planar_out || !ok(bitdepth) || !ok(input_bitdepth) || input_bitdepth > bitdepth) return 1;
+  if (!scale_args_resolved(scale, layout, w, h, input_bitdepth, L) || (uintptr_t)src % (input_bitdepth > 8 ? 2 : 1)) return 1;
+  static const thor_hip_frame_layout packed = {sizeof(thor_hip_frame_layout), THOR_HIP_CHROMA_PLANAR, 0, 0, 0, 0, 0};
+  const thor_hip_frame_layout* l = layout ? layout : &packed;
+  ScalePlan P;
+  if (!resolve_scale(scale->src_width, scale->src_height, scale->filter, scale->chroma_site, l->chroma, l->msb_aligned, l->pitch_y, l->pitch_c, l->offset_u, l->offset_v,
+                     w, h, input_bitdepth, P))
+    return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_scale_in<uint8_t>(src, P, w, h, input_bitdepth, bitdepth, (uint8_t*)planar_out);
+  else kat_scale_in<uint16_t>(src, P, w, h, input_bitdepth, bitdepth, (uint16_t*)planar_out);
+  return 0;
+}
 // k_rgb_in / k_rgb_out on host buffers, like the two above: the device copy keeps the host pointer's offset from a 16-byte boundary.
 static int kat_rgb_args(const void* rgb, const void* planar, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, RgbFormat& R) {
   auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };

@@ -230,4 +230,31 @@ template <typename PIX, typename DST>
 __global__ __launch_bounds__(256) void k_rgb_out(Plane3<PIX> src, void* frame, RgbFormat R, int width, int height, int shift) {
   rgb_out_rows<PIX, DST>(src, frame, R, width, height, shift, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x, 256);
 }
+
+// ---- frames of another size (tk_scale.h: scale_load_row, scale_hfilter_row, scale_vfilter) --------
+// One frame per launch, all three planes: one workgroup per tile of SCALE_TW x SCALE_TH destination samples (luma tiles, then U, then V).  Each of
+// the four wavefronts takes every fourth source row the tile needs: 16-byte vectors of it into the wavefront's row buffer, the horizontal taps from
+// there into `inter`; then all 256 lanes filter `inter` vertically and write the plane.  LDS: the row buffers and the tile's horizontal
+// coefficients (static), the intermediate rows (dynamic: `vrows` of the plan x SCALE_TW x 2 bytes, at most 36 KiB).  The intermediate never leaves LDS.
+template <typename SRC, typename PIX>
+__global__ __launch_bounds__(256) void k_scale_in(const void* frame, PixLayout L, ScaleTables tab, Plane3<PIX> dst, int src_w, int width, int height, int maxv, int up) {
+  __shared__ __attribute__((aligned(16))) int16_t rowbuf[SCALE_WAVES * SCALE_ROWCAP];
+  __shared__ __attribute__((aligned(16))) int16_t coef[SCALE_MAX_TAPS * SCALE_TW];
+  extern __shared__ __attribute__((aligned(16))) int16_t inter[];
+  const int tid = (int)threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const bool luma = (int)blockIdx.x < scale_tiles(width, height);
+  const ScaleAxis H = luma ? tab.a[0] : tab.a[2];
+  const ScaleAxis V = luma ? tab.a[1] : tab.a[3];
+  const ScaleTile t = scale_tile((int)blockIdx.x, width, height, H, V);
+  const ScaleSrc s = scale_src(frame, L, t.plane, src_w);
+  scale_stage_coef(H, t, coef, tid, 256);
+  __syncthreads();
+  for (int r = 0; r < t.nrows; r += SCALE_WAVES) {   // t.nrows is the same in every lane: the barriers are met by all
+    if (r + wave < t.nrows) scale_load_row<SRC>(s, L.msb, t.r0 + r + wave, t.klo, t.khi, rowbuf + wave * SCALE_ROWCAP, lane, 64);
+    __syncthreads();
+    if (r + wave < t.nrows) scale_hfilter_row(H, t, coef, rowbuf + wave * SCALE_ROWCAP, inter + (r + wave) * SCALE_TW, lane, 64);
+    __syncthreads();
+  }
+  scale_vfilter<PIX>(V, t, inter, scale_plane(dst, t.plane), t.plane ? dst.sc : dst.sy, maxv, up, tid, 256);
+}
 }  // namespace tk

@@ -25,6 +25,11 @@ struct CliArgs {
   int rgb_full = 0;          // -rgbrange limited|full
   int rgb_site = 1;          // -rgbsite centre|left
   bool rgb_given = false;    // one of the three was given: front-end options like -pixfmt
+  // -if frames of another size, resampled to -width x -height on the device (tk_scale.h); -pixfmt then describes them at that size, -rf stays at the coded size
+  int src_w = 0, src_h = 0;  // -src_width, -src_height (0: the coded size)
+  int scale_filter = 1;      // -scale_filter bilinear|bicubic
+  int scale_site = 1;        // -scale_site left|centre
+  bool scale_given = false;  // one of the four was given: front-end options like -pixfmt
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -74,6 +79,15 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
       if (k == "-rgbmatrix") { a.rgb_matrix = v == "601" ? 0 : v == "709" ? 1 : 2; ok = v == "601" || v == "709" || v == "2020"; }
       else if (k == "-rgbrange") { a.rgb_full = v == "full"; ok = v == "full" || v == "limited"; }
       else { a.rgb_site = v == "left"; ok = v == "left" || v == "centre"; }
+      if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
+    else if (k == "-src_width" || k == "-src_height" || k == "-scale_filter" || k == "-scale_site") {
+      a.scale_given = true;
+      bool ok = true;
+      if (k == "-src_width") { a.src_w = I(); ok = a.src_w > 0; }
+      else if (k == "-src_height") { a.src_h = I(); ok = a.src_h > 0; }
+      else if (k == "-scale_filter") { a.scale_filter = v == "bicubic"; ok = v == "bicubic" || v == "bilinear"; }
+      else { a.scale_site = v == "left"; ok = v == "left" || v == "centre"; }
       if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
     }
     else if (k == "-width") p.width = I();
@@ -188,13 +202,28 @@ template <typename PIX> int cli_run(const CliArgs& a) {
     fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", a.pixfmt.c_str());
     return 2;
   }
+  // -src_width / -src_height: the -if frames have that size, in the -pixfmt layout, and are resampled while they are staged
+  const bool use_scale = a.scale_given;
+  const int src_w = a.src_w ? a.src_w : p.width, src_h = a.src_h ? a.src_h : p.height;
+  const int src_chroma = a.pixfmt == "i420" ? 0 : a.pixfmt == "nv21" ? 2 : 1, src_msb = a.pixfmt == "p010";
+  PixLayout slay;
+  if (use_scale && (use_rgb || !resolve_scale_args(src_w, src_h, a.scale_filter, a.scale_site, src_chroma, src_msb, 0, 0, 0, 0, p.width, p.height, p.input_bitdepth, slay))) {
+    fprintf(stderr, "Run-time error...\n-src_width %d -src_height %d with -pixfmt %s cannot be resampled to %dx%d\n...now exiting to system...\n", src_w, src_h,
+            a.pixfmt.c_str(), p.width, p.height);
+    return 2;
+  }
   FILE* fi = fopen(a.infile.c_str(), "rb");
   if (!fi) { fprintf(stderr, "cannot open %s\n", a.infile.c_str()); return 2; }
   Engine<PIX> eng;
   eng.frame_distortion = a.snrcalc != 0;
   eng.open(p, a.streams);
-  const size_t fsz = use_rgb ? rgb.bytes : eng.frame_bytes();  // the files hold input-depth samples (-if and -rf: common/common_frame.c:484-650), or RGB frames
-  std::vector<uint8_t> frame(fsz), rec(fsz);
+  if (use_scale && !eng.resolve_scaled(src_w, src_h, a.scale_filter, a.scale_site, src_chroma, src_msb, 0, 0, 0, 0)) {
+    fprintf(stderr, "Run-time error...\nno tap table for %dx%d -> %dx%d\n...now exiting to system...\n", src_w, src_h, p.width, p.height);
+    return 2;
+  }
+  const size_t rsz = use_rgb ? rgb.bytes : eng.frame_bytes();  // the files hold input-depth samples (-if and -rf: common/common_frame.c:484-650), or RGB frames
+  const size_t fsz = use_scale ? slay.bytes : rsz;             // -if at the source size
+  std::vector<uint8_t> frame(fsz), rec(rsz);
   std::vector<FILE*> fr(a.streams, nullptr);
   auto name = [&](const std::string& base, int s) { return a.streams == 1 ? base : base + "." + std::to_string(s); };
   for (int s = 0; s < a.streams; s++)
@@ -204,7 +233,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   const int file_frames = (int)(ftell(fi) / (long)fsz);
   for (int s = 0; s < a.streams; s++) eng.begin_sequence(s, a.skip + s * a.num_frames, a.num_frames, file_frames);
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
-  auto upload = [&](int s) { if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
+  auto upload = [&](int s) { if (use_scale) eng.stage_scaled_host(frame.data(), eng.st[s].orig.p); else if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
   auto download = [&](int s) { if (use_rgb) eng.fetch_rgb_host(eng.st[s].rec.p, rec.data(), rgb); else if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
   // THOR_STAGGER=1 (tests): the streams in two groups half a frame apart (Engine::encode_run) instead of lock step
   if (getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER")) && a.streams > 1) {
@@ -264,7 +293,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
     if (fr[s])
       for (int n = 0; n < a.num_frames; n++) {
         const std::vector<uint8_t>& r = recs[(size_t)s * a.num_frames + n];
-        if (!r.empty()) fwrite(r.data(), 1, fsz, fr[s]);
+        if (!r.empty()) fwrite(r.data(), 1, rsz, fr[s]);
       }
   for (int s = 0; s < a.streams; s++) {
     if (fr[s]) fclose(fr[s]);

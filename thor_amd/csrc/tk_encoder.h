@@ -19,6 +19,7 @@
 #include "tk_interp_dev.h"
 #include "tk_clpf.h"
 #include "tk_filters.h"
+#include "tk_scale.h"
 #include "tk_report.h"
 
 namespace tk {
@@ -76,6 +77,9 @@ template <typename PIX> void launch_layout_out(const Plane3<PIX>& src, void* fra
 // An RGB frame (tk_filters.h: RgbFormat, rgb_in_rows, rgb_out_rows) <-> planes at the engine's depth, one launch each on the library's stream.
 template <typename PIX> void launch_rgb_in(const void* frame, const RgbFormat& R, const Plane3<PIX>& dst, int width, int height, int bitdepth, int input_bitdepth);
 template <typename PIX> void launch_rgb_out(const Plane3<PIX>& src, void* frame, const RgbFormat& R, int width, int height, int bitdepth, int input_bitdepth);
+// A frame of another size (tk_scale.h: ScalePlan, k_scale_in) -> planes at the engine's depth, one launch on the library's stream.
+template <typename PIX> void launch_scale_in(const void* frame, const PixLayout& L, const ScaleTables& tab, int vrows, const Plane3<PIX>& dst, int src_w, int width,
+                                             int height, int bitdepth, int input_bitdepth);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -423,6 +427,10 @@ template <typename PIX> class Engine {
   void* d_packed = nullptr;             // input_bitdepth < bitdepth: one packed frame of input-depth samples, staging for upload_orig / download_rec
   void* d_layout = nullptr;             // a host frame in a caller's layout, as it came (stage_layout_host / fetch_layout_host); allocated on first use
   size_t d_layout_bytes = 0;
+  ScalePlan scale_plan;                 // the most recent scaled staging (resolve_scaled), its tables in device memory and whether those are stale
+  void* d_scale = nullptr;
+  ScaleTables scale_tab;
+  bool scale_dirty = true;
 
   // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
   int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
@@ -536,6 +544,7 @@ template <typename PIX> class Engine {
     backend::dev_free(d_sse); d_sse = nullptr;
     backend::dev_free(d_packed); d_packed = nullptr;
     backend::dev_free(d_layout); d_layout = nullptr; d_layout_bytes = 0;
+    backend::dev_free(d_scale); d_scale = nullptr; scale_dirty = true;
   }
 
   // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
@@ -645,6 +654,41 @@ template <typename PIX> class Engine {
     backend::d2h(tmp.data(), d_layout, R.bytes);
     for (int k = 0; k < (R.kind == 2 ? 3 : 1); k++)
       for (int i = 0; i < sp.height; i++) memcpy((uint8_t*)frame + k * R.plane + i * R.pitch, &tmp[k * R.plane + i * R.pitch], row);
+  }
+
+  // A frame of another size (tk_scale.h): resolve_scaled checks the caller's description against this engine's pictures and keeps the plan - its
+  // tables are rebuilt only when the source size, the filter or the site changed, and travel to the device only then.  false: refused, nothing
+  // changed on the device.  scale_in then resamples a frame in device memory into planes at the engine's depth (asynchronous on the device).
+  bool resolve_scaled(int src_w, int src_h, int filter, int site, int chroma, int msb_aligned, long long pitch_y, long long pitch_c, size_t off_u, size_t off_v) {
+    bool rebuilt = false;
+    const bool ok = resolve_scale(src_w, src_h, filter, site, chroma, msb_aligned, pitch_y, pitch_c, off_u, off_v, sp.width, sp.height, sp.input_bitdepth, scale_plan, &rebuilt);
+    if (rebuilt || !ok) scale_dirty = true;
+    return ok;
+  }
+  void scale_in(const void* frame, const Plane3<PIX>& dst) {
+    const ScalePlan& P = scale_plan;
+#if TK_HOST
+    const ScaleTables tab = P.host_tables();
+    if (sp.input_bitdepth == 8) scale_in_host<uint8_t, PIX>(frame, P.L, tab, dst, P.src_w, sp.width, sp.height, sp.input_bitdepth, depth_shift(), 1, 1);
+    else if constexpr (sizeof(PIX) == 2) scale_in_host<uint16_t, PIX>(frame, P.L, tab, dst, P.src_w, sp.width, sp.height, sp.input_bitdepth, depth_shift(), 1, 1);
+#else
+    if (scale_dirty) {  // the device copy of the most recent plan
+      std::vector<uint8_t> h(P.blob_bytes());
+      backend::dev_sync();
+      backend::dev_free(d_scale);
+      d_scale = backend::dev_alloc(h.size());
+      scale_tab = P.pack(h.data(), (const uint8_t*)d_scale);
+      backend::h2d(d_scale, h.data(), h.size());
+      scale_dirty = false;
+    }
+    launch_scale_in<PIX>(frame, P.L, scale_tab, P.t[1].span > P.t[3].span ? P.t[1].span : P.t[3].span, dst, P.src_w, sp.width, sp.height, sp.bitdepth, sp.input_bitdepth);
+#endif
+  }
+  // The same for a frame in host memory, through the device buffer of the layouts (layout_buf).  Synchronous.
+  void stage_scaled_host(const void* frame, const Plane3<PIX>& dst) {
+    backend::h2d(layout_buf(scale_plan.L.bytes), frame, scale_plan.L.bytes);
+    scale_in(d_layout, dst);
+    backend::dev_sync();
   }
 
   // planar 4:2:0 frame of input-depth samples in host memory -> device `orig` of stream s

@@ -3,12 +3,15 @@
  *   thorenc_hip -cf config.txt -if in.yuv -width W -height H -qp Q -n N [-skip K] [-f fps]
  *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-pixfmt i420|nv12|nv21|p010|rgba|bgra|rgb24|bgr24] [-name value ...]
  *               [-rgbmatrix 601|709|2020] [-rgbrange limited|full] [-rgbsite centre|left]
+ *               [-src_width W -src_height H] [-scale_filter bilinear|bicubic] [-scale_site left|centre]
  * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
  * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
  * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
  * rgba / bgra / rgb24 / bgr24: the files hold RGB frames - one byte per channel with 8-bit input, else 16-bit words with the value in the low
  * bits - converted on the device (thor_hip_stage_frame_rgb / thor_hip_get_recon_rgb) with -rgbmatrix (default 709), -rgbrange (limited) and
  * -rgbsite (left).
+ * -src_width / -src_height: the -if frames have that size (in the -pixfmt layout, which must not be RGB) and are resampled to -width x -height on
+ * the device while they are staged (thor_hip_stage_frame_scaled; defaults bicubic, left); -rf stays at the coded size.
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -50,6 +53,8 @@ int main(int argc, char** argv) {
   const char* statf = NULL;
   const char* pixfmt = "i420";
   const char *rgbmatrix = "709", *rgbrange = "limited", *rgbsite = "left";
+  const char *scalefilter = "bicubic", *scalesite = "left";
+  int src_w = 0, src_h = 0, scaled = 0;
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -70,6 +75,10 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-rgbmatrix")) rgbmatrix = v;
     else if (!strcmp(k, "-rgbrange")) rgbrange = v;
     else if (!strcmp(k, "-rgbsite")) rgbsite = v;
+    else if (!strcmp(k, "-src_width")) { src_w = atoi(v); scaled = 1; }
+    else if (!strcmp(k, "-src_height")) { src_h = atoi(v); scaled = 1; }
+    else if (!strcmp(k, "-scale_filter")) { scalefilter = v; scaled = 1; }
+    else if (!strcmp(k, "-scale_site")) { scalesite = v; scaled = 1; }
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -96,17 +105,23 @@ int main(int argc, char** argv) {
   }
   else if (lay) { fprintf(stderr, "Run-time error...\noption -pixfmt %s is unknown\n...now exiting to system...\n", pixfmt); return 2; }
   if (lay && p.input_bitdepth <= 8 && layout.msb_aligned) { fprintf(stderr, "Run-time error...\n-pixfmt %s needs input_bitdepth above 8\n...now exiting to system...\n", pixfmt); return 2; }
+  thor_hip_scale scale = {sizeof(thor_hip_scale), src_w ? src_w : p.width, src_h ? src_h : p.height,
+                          !strcmp(scalefilter, "bicubic") ? THOR_HIP_SCALE_BICUBIC : !strcmp(scalefilter, "bilinear") ? THOR_HIP_SCALE_BILINEAR : -1,
+                          !strcmp(scalesite, "left") ? 1 : !strcmp(scalesite, "centre") ? 0 : -1};
+  if (scaled && (scale.filter < 0 || scale.chroma_site < 0)) { fprintf(stderr, "Run-time error...\noption -scale_filter %s -scale_site %s is unknown\n...now exiting to system...\n", scalefilter, scalesite); return 2; }
+  if (scaled && (rgb || !thor_hip_scale_bytes_for(p.width, p.height, p.input_bitdepth, &scale, lay))) { fprintf(stderr, "Run-time error...\n-src_width %d -src_height %d with -pixfmt %s cannot be resampled to %dx%d\n...now exiting to system...\n", scale.src_width, scale.src_height, pixfmt, p.width, p.height); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
   size_t fsz = rgb ? thor_hip_rgb_bytes(e, rgb) : thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth, or RGB frames */
-  unsigned char* frame = (unsigned char*)malloc(fsz);
+  size_t isz = scaled ? thor_hip_scale_bytes(e, &scale, lay) : fsz;        /* -if at the source size */
+  unsigned char* frame = (unsigned char*)malloc(isz);
   thor_hip_set_frame_distortion(e, snrcalc != 0);
   for (int s = 0; s < S; s++)
     for (int f = 0; f < n; f++) {
       size_t idx = (size_t)skip + (size_t)s * n + f;
       if (wrap > 0) idx %= (size_t)wrap;
-      if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame, 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); return 4; }
-      if (rgb ? thor_hip_stage_frame_rgb(e, s, f, frame, rgb, 0) : lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
+      if (fseek(fi, (long)(idx * isz), SEEK_SET) || fread(frame, 1, isz, fi) != isz) { fprintf(stderr, "short read at frame %zu\n", idx); return 4; }
+      if (scaled ? thor_hip_stage_frame_scaled(e, s, f, frame, &scale, lay, 0) : rgb ? thor_hip_stage_frame_rgb(e, s, f, frame, rgb, 0) : lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
     }
   FILE** fr = (FILE**)calloc(S, sizeof(FILE*));
   char name[4096];
@@ -117,7 +132,7 @@ int main(int argc, char** argv) {
   int* slots = (int*)malloc(S * sizeof(int));
   /* coding-order schedule (B frames are coded out of display order); recon is written in display order */
   fseek(fi, 0, SEEK_END);
-  long file_frames = wrap > 0 ? (long)skip + (long)S * n : (long)(ftell(fi) / (long)fsz);
+  long file_frames = wrap > 0 ? (long)skip + (long)S * n : (long)(ftell(fi) / (long)isz);
   for (int s = 0; s < S; s++)
     if (thor_hip_begin_sequence(e, s, skip + s * n, n, (int)file_frames)) { fprintf(stderr, "bad sequence bounds\n"); return 5; }
   unsigned char** recs = (unsigned char**)calloc((size_t)S * n, sizeof(unsigned char*));
