@@ -402,6 +402,16 @@ int thor_hip_kat_clpf(const void* rec_yuv, const void* org_yuv, int width, int h
 /* interpolate_frames(new, ref0, ref1, 2, 1) (common/temporal_interp.c:909: the frame half way between two reference pictures; luma pyramid,
  * block motion estimation per level, merge, motion-compensated average) through the engine's own device path (tk_interp_dev.h). */
 int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv);
+/* The same path stage by stage, for `n_streams` (1..4) reference pairs of one geometry in ONE Engine::make_interp_frames call (every launch covers all streams;
+ * each stream has its own row dispenser and progress counters).  yuv0 / yuv1: n_streams packed planar 4:2:0 frames each.  levels: the number of pyramid
+ * levels, min(4, (int)(log2(min(width, height)) - 4)) - the caller sizes the buffers with it, a different count in the engine returns 2.  Copied back per
+ * stream, streams one after the other:
+ *   pyramid     reference 0 then 1, for each level l = 1 .. levels-1 its luma plane with the padding of 32: (height >> l) + 64 rows of (width >> l) + 64 samples;
+ *   nmv         for each level l = 0 .. levels-1 the final fields nmv[0] then nmv[1] (after the merge pass): bw * bh (x, y) pairs each, bw = 2 * ceil((width >> l) / 16);
+ *   out_padded  the interpolated picture with its borders: Y (height + 320 rows of width + 320), then U and V (height / 2 + 160 rows of width / 2 + 160).
+ * width, height: multiples of 8, 64..8192.  Known answers recorded from the reference stage by stage: tests/golden/gen_kat12.py -> kat12*.npz. */
+int thor_hip_kat_interp_stages(int n_streams, const void* yuv0, const void* yuv1, int width, int height, int bitdepth, int levels, void* pyramid, int16_t* nmv,
+                               void* out_padded);
 
 /* The motion search of one prediction unit - motion_estimate (enc/encode_block.c:517-711: telescope, candidate list incl. the 5-offset widesad of 16x16
  * blocks, hexagon refinement, half- and quarter-pel passes, the encoder_speed 1 / 2 approximations) - on `n` items of one current / reference luma frame pair

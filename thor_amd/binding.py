@@ -661,6 +661,23 @@ def kat_interpolate(yuv0, yuv1, width, height, bitdepth=8):
     return out
 
 
+def kat_interp_stages(yuv0, yuv1, width, height, bitdepth=8):
+    """thor_hip_kat_interp_stages: yuv0 / yuv1 (S, width * height * 3 / 2) packed planar frames, one reference pair per stream, all through one
+    make_interp_frames call.  Returns the raw buffers, one row per stream: pyramid planes with padding, nmv[0] / nmv[1] of every level, the padded output
+    (layout: include/thor_hip.h)."""
+    import math
+    T = _pix(bitdepth)
+    a = np.ascontiguousarray(yuv0, dtype=T); b = np.ascontiguousarray(yuv1, dtype=T)
+    S = len(a)
+    assert a.shape == b.shape == (S, width * height * 3 // 2)
+    levels = min(4, int(math.log10(min(width, height)) / math.log10(2.0) - 4.0))
+    pyr = np.zeros((S, 2 * sum(((height >> l) + 64) * ((width >> l) + 64) for l in range(1, levels))), dtype=T)
+    nmv = np.zeros((S, sum(16 * (((width >> l) + 15) // 16) * (((height >> l) + 15) // 16) for l in range(levels))), dtype=np.int16)
+    out = np.zeros((S, (height + 320) * (width + 320) + 2 * (height // 2 + 160) * (width // 2 + 160)), dtype=T)
+    _kat('thor_hip_kat_interp_stages', S, _vp(a), _vp(b), width, height, bitdepth, levels, _vp(pyr), _vp(nmv), _vp(out))
+    return pyr, nmv, out
+
+
 def kat_motion_estimate(cur, ref, par, lam, cand, bitdepth=8):
     """thor_hip_kat_motion_estimate: the device motion search on len(par) items of one current / reference luma pair; returns (n, 3) mv.x, mv.y, cost."""
     T = _pix(bitdepth)

@@ -2,6 +2,7 @@
 // translation unit thor_hip.cpp: the kernels here run the very device functions the superblock kernel calls).
 #pragma once
 #include "tk_kat_bits.h"
+#include "tk_kat_interp.h"
 namespace tk {
 // The kernels behind the known-answer entry points run the product's device code on one block / transform unit per workgroup of
 // one wavefront; PIX = uint8_t (the reference's _lbd functions) or uint16_t (_hbd, bitdepth 9..12).
@@ -859,6 +860,14 @@ extern "C" int thor_hip_kat_rgb_out(const void* planar_in, const thor_hip_rgb_fo
 extern "C" int thor_hip_kat_interpolate(const void* yuv0, const void* yuv1, int width, int height, int bitdepth, void* out_yuv) {
   KAT_BD(kat_interpolate<uint8_t>((const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, (uint8_t*)out_yuv),
          kat_interpolate<uint16_t>((const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, (uint16_t*)out_yuv));
+}
+// The same path for n_streams reference pairs in one make_interp_frames call, with every stage copied back (tk_kat_interp.h; tests/golden/gen_kat12.py)
+extern "C" int thor_hip_kat_interp_stages(int n_streams, const void* yuv0, const void* yuv1, int width, int height, int bitdepth, int levels, void* pyramid,
+                                          int16_t* nmv, void* out_padded) {
+  if (bitdepth < 8 || bitdepth > 12) return 1;
+  if (!ensure_init_any()) return 3;
+  KAT_BD(kat_interp_stages<uint8_t>(n_streams, (const uint8_t*)yuv0, (const uint8_t*)yuv1, width, height, 8, levels, (uint8_t*)pyramid, nmv, (uint8_t*)out_padded),
+         kat_interp_stages<uint16_t>(n_streams, (const uint16_t*)yuv0, (const uint16_t*)yuv1, width, height, bitdepth, levels, (uint16_t*)pyramid, nmv, (uint16_t*)out_padded));
 }
 
 // Resources of the superblock kernel as the runtime sees them (a guard against silent occupancy regressions: round 6 found the 8-bit kernel at 227 VGPRs =
