@@ -282,6 +282,65 @@ int thor_hip_stage_frame_scaled(thor_hip_encoder* e, int stream, int slot, const
  * the coefficients.  Returns the count; 0 = refused (S or T outside 1 .. 8192, ratio above 8, unknown filter, i outside [0, T), cap too small). */
 int thor_hip_scale_taps(int S, int T, int filter, int cosited, int i, int* first, short* coeff, int cap);
 
+/* Rate control: a target bitrate per stream.  This is the library's own rate control, not the reference's (-bitrate / -max_delta_qp change the QP after every
+ * superblock in raster order and stay refused, thor_hip_params_set returns 2): it picks ONE base QP per frame, so every frame is exactly what the block path
+ * produces at that QP, the stream is an ordinary Thor stream and the reference decoder reproduces the reconstruction.  Integers only, except the one line that
+ * forms T; everything below is normative, and tests/rc_model.py restates it.
+ *
+ * Analysis (k_rc_cost, one launch per group of frames, before the frame's jobs are set up; nothing is launched for a stream without rate control).  The luma of
+ * the staged original at the engine's depth is halved: h(x, y) = (Y(2x, 2y) + Y(2x + 1, 2y) + Y(2x, 2y + 1) + Y(2x + 1, 2y + 1) + 2) >> 2, a plane of width / 2 x
+ * height / 2 samples kept per stream until the next frame's analysis (two planes alternate).  That plane is cut into 8x8 blocks from its top-left corner; width and height
+ * are multiples of 8, so a block at the right / bottom edge may be 4 wide / high and is evaluated on the n samples inside the plane.  Per block:
+ *   intra = sum |h - m|, m = (sum h + n / 2) / n                                    (integer division)
+ *   inter = min over (dx, dy) in [-8, 8]^2 of sum |h(x, y) - h_prev(x + dx, y + dy)|, over the vectors whose displaced block lies wholly inside the previous
+ *           plane (no padding; the zero vector always does).  h_prev: the plane of the frame analysed before this one for the stream, in CODING order.  The first
+ *           frame of a stream, and the first after thor_hip_begin_sequence or thor_hip_set_rate_control, has none: inter = intra.
+ * Per frame three exact 64-bit sums over the blocks: sum_intra = sum intra, sum_best = sum min(intra, inter), n_intra = the number of blocks with intra < inter.
+ *
+ * Controller, per stream.  T = (long long)((double)bitrate / (double)frame_rate), at least 1; B = bitrate * buffer_ms / 1000, at least 1.  State, all zero when
+ * a sequence begins: fullness F, the overflow count, the frame count, and per frame class c (0: I, 1: P, 2..5: B of level 0, 1, 2, 3 and deeper) a count n[c], a
+ * factor f[c] (Q16) and an average a[c] of the frame's bits.  step(q) = 2^((q - 4) / 6) in Q16, the 52 literal values of thor_amd/csrc/tk_rc.h.  A frame's cost
+ * is sum_intra for an I frame and sum_best otherwise, clamped to 1 .. 2^36; with factors of at most 2^26 no product below reaches 2^63.  All divisions are integer divisions of non-negative values, except F / span, which rounds
+ * towards zero.
+ *   qp(b)      the QP of the frame at base QP b: the reference's per-frame formula (enc/mainenc.c:281-314: dqpI; mqpP / dqpP off the HQperiod grid; mqpB* / dqpB* by
+ *              B level; clamped to 0..51) with b in the place of -qp.  Without rate control b is -qp itself: the same function serves both.
+ *   decision   the stream's first frame: b = initial_qp (0: the parameter set's qp).  Otherwise with [lo, hi] = [min_qp, max_qp] ([min_qp_i, max_qp_i] for an I frame):
+ *                budget = T * 4 for an I frame; T * a[c] / max(1, (sum over c' >= 1 of n[c'] * a[c']) / (sum of n[c'])) when n[c] > 0; else T
+ *                budget = max(budget - F / max(1, B / (2 * T)), T / 8)               (the fullness is paid back over half the buffer)
+ *                b = the lowest b in [lo, hi) with (n[c] > 0 ? f[c] : f0[c]) * cost / step(qp(b)) <= budget, else hi;   f0 = {296000, 217000, 216000, 188000, 174000, 174000}
+ *   update     after the frame is coded at q = qp(b) with `bits` bits (thor_hip_frame_stats.num_bits: without the 4-byte framing and the sequence header):
+ *                o = clamp(bits * step(q) / cost, 1, 2^26);   f[c] = n[c] > 0 ? (f[c] + o) / 2 : o;   a[c] = n[c] > 0 ? (3 * a[c] + bits) / 4 : bits;   n[c] += 1;
+ *                when the n sum to 65536 each becomes (n + 1) / 2;   F = max(F + bits - T, -B);   a frame that ends with F > B counts as an overflow.
+ * The chosen QP is the frame's QP everywhere: block decisions and lambda, deblocking, CDEF, CLPF, the frame header, thor_hip_frame_stats.qp and the report. */
+typedef struct thor_hip_rate_control {
+  int size;         /* sizeof(thor_hip_rate_control) */
+  int bitrate;      /* bits per second; 0 = off */
+  int buffer_ms;    /* the virtual buffer in milliseconds of the bitrate; 0 = 1000 */
+  int min_qp;       /* base QP range of inter frames; min_qp == max_qp == 0 means 0..51 */
+  int max_qp;
+  int min_qp_i;     /* the same for I frames */
+  int max_qp_i;
+  int initial_qp;   /* base QP of the first frame of a sequence; 0 = the parameter set's qp */
+} thor_hip_rate_control;
+/* 0 when thor_hip_set_rate_control would accept *rc (NULL included: it means off); 1 otherwise: `size` is wrong, a value is negative, a minimum is above its
+ * maximum, a QP is above 51.  Needs no encoder and no device. */
+int thor_hip_rate_control_check(const thor_hip_rate_control* rc);
+/* Turn rate control on for one stream (each stream has its own target; NULL or bitrate 0: off).  Legal before the stream's first frame and right after
+ * thor_hip_begin_sequence, which keeps the target and restarts the controller.  Returns 0; 1 for a bad argument or a refused *rc, 2 when the stream is in the
+ * middle of a sequence - nothing is touched then.  While it is off for every stream the encoder launches, copies, allocates and synchronises exactly as before. */
+int thor_hip_set_rate_control(thor_hip_encoder* e, int stream, const thor_hip_rate_control* rc);
+typedef struct thor_hip_frame_rc {
+  int base_qp;                     /* the controller's choice; thor_hip_frame_stats.qp is qp(base_qp) */
+  int frame_class;                 /* 0: I, 1: P, 2..5: B of level 0, 1, 2, 3 and deeper */
+  unsigned long long sum_intra, sum_best, n_intra;
+  long long fullness;              /* F after this frame */
+  long long buffer_bits;           /* B */
+  long long target_bits;           /* T */
+  int overflows;                   /* frames so far that ended with F > B */
+} thor_hip_frame_rc;
+/* Record i (coding order, the index of thor_hip_get_frame_stats) of a rate-controlled stream.  Returns 0; 1 on a bad argument or a stream without rate control. */
+int thor_hip_get_frame_rc(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_rc* out);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -505,6 +564,11 @@ int thor_hip_kat_layout_out(const void* planar_in, const thor_hip_frame_layout* 
  * the packed planar w x h frame at `bitdepth`.  Same return values. */
 int thor_hip_kat_scale_in(const void* src, const thor_hip_scale* scale, const thor_hip_frame_layout* layout, int w, int h, int input_bitdepth, int bitdepth,
                           void* planar_out);
+/* k_rc_cost, the frame analysis of rate control, as the engine launches it for two consecutive frames of one stream: first on `prev` (when given) without a
+ * previous plane, then on `cur` against the half-size plane the first launch wrote.  cur / prev_or_null: luma planes of w x h samples, w samples per row (bytes
+ * for bitdepth 8, uint16_t for 10 / 12); w, h: multiples of 8, at least 16.  out: sum_intra, sum_best, n_intra of `cur`; half_out: its half-size plane, w / 2 x
+ * h / 2 samples of the same type.  Returns 0, 1 = bad argument, 3 = no device. */
+int thor_hip_kat_rc_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3], void* half_out);
 /* The same for k_rgb_in / k_rgb_out: `src` / `dst` hold thor_hip_rgb_bytes_for(w, h, fmt) bytes in `fmt` (dst: plus 64 guard bytes, all of it uploaded
  * before the kernel runs and downloaded afterwards); the planar frames are at `bitdepth` (k_rgb_out rounds back to input_bitdepth first).  Any depth
  * of `fmt` goes with any input_bitdepth <= bitdepth.  Same return values. */

@@ -148,6 +148,26 @@ class Scale(C.Structure):
         super().__init__(C.sizeof(Scale), src_width, src_height, filter, chroma_site)
 
 
+class RateControl(C.Structure):
+    """thor_hip_rate_control (include/thor_hip.h): a target bitrate in bits per second for one stream, the virtual buffer in milliseconds (0 = 1000),
+    the base-QP ranges of inter and of I frames (0 / 0 = 0..51) and the base QP of a sequence's first frame (0 = the parameter set's qp)."""
+    _fields_ = [('size', C.c_int), ('bitrate', C.c_int), ('buffer_ms', C.c_int), ('min_qp', C.c_int), ('max_qp', C.c_int), ('min_qp_i', C.c_int),
+                ('max_qp_i', C.c_int), ('initial_qp', C.c_int)]
+
+    def __init__(self, bitrate=0, buffer_ms=0, min_qp=0, max_qp=0, min_qp_i=0, max_qp_i=0, initial_qp=0):
+        super().__init__(C.sizeof(RateControl), bitrate, buffer_ms, min_qp, max_qp, min_qp_i, max_qp_i, initial_qp)
+
+    def ok(self):
+        """thor_hip_rate_control_check: would thor_hip_set_rate_control accept it?  Needs no device."""
+        return lib().thor_hip_rate_control_check(C.byref(self)) == 0
+
+
+class FrameRc(C.Structure):
+    """thor_hip_frame_rc (include/thor_hip.h): one coded frame of a rate-controlled stream."""
+    _fields_ = [('base_qp', C.c_int), ('frame_class', C.c_int), ('sum_intra', C.c_ulonglong), ('sum_best', C.c_ulonglong), ('n_intra', C.c_ulonglong),
+                ('fullness', C.c_longlong), ('buffer_bits', C.c_longlong), ('target_bits', C.c_longlong), ('overflows', C.c_int)]
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -214,6 +234,10 @@ def lib():
         L.thor_hip_stage_frame_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, SP, LP, C.c_int]
         L.thor_hip_scale_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_short), C.c_int]
         L.thor_hip_kat_scale_in.argtypes = [C.c_void_p, SP, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_rate_control_check.argtypes = [C.POINTER(RateControl)]
+        L.thor_hip_set_rate_control.argtypes = [C.c_void_p, C.c_int, C.POINTER(RateControl)]
+        L.thor_hip_get_frame_rc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameRc)]
+        L.thor_hip_kat_rc_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.c_void_p]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -476,6 +500,25 @@ class Encoder:
             out.append({'display_index': f.display_index, 'type': 'IPB'[f.frame_type], 'qp': f.qp, 'num_bits': f.num_bits,
                         'ref_array': list(f.ref_array)[:nr], 'ref_frame_num': list(f.ref_frame_num)[:nr], 'has_sse': bool(f.has_sse),
                         'sse': [int(v) for v in f.sse], 'psnr': [float(v) for v in f.psnr]})
+        return out
+
+    def set_rate_control(self, stream, rc):
+        """Rate control of one stream (a RateControl; None or bitrate 0: off): thor_hip_set_rate_control.  Legal before the stream's first frame and
+        right after begin_sequence; raises ValueError when the library refuses."""
+        r = lib().thor_hip_set_rate_control(self.h, stream, C.byref(rc) if rc is not None else None)
+        if r:
+            raise ValueError('rate control refused: ' + ('the stream is in the middle of a sequence' if r == 2 else 'bad stream or values'))
+
+    def frame_rc(self, stream):
+        """The controller's log of a rate-controlled stream in coding order (thor_hip_get_frame_rc), index for index with frame_stats: a list of
+        dicts; empty for a stream without rate control."""
+        L, out, f = lib(), [], FrameRc()
+        for i in range(L.thor_hip_frame_stats_count(self.h, stream)):
+            if L.thor_hip_get_frame_rc(self.h, stream, i, C.byref(f)):
+                break
+            out.append({'base_qp': f.base_qp, 'frame_class': f.frame_class, 'sum_intra': int(f.sum_intra), 'sum_best': int(f.sum_best),
+                        'n_intra': int(f.n_intra), 'fullness': int(f.fullness), 'buffer_bits': int(f.buffer_bits), 'target_bits': int(f.target_bits),
+                        'overflows': f.overflows})
         return out
 
     def report(self, stream):
@@ -911,3 +954,18 @@ def kat_scale_in(src, scale, width, height, input_bitdepth, bitdepth, layout=Non
     out = np.zeros(width * height * 3 // 2, dtype=_pix(bitdepth))
     _kat('thor_hip_kat_scale_in', _vp(src), C.byref(scale), C.byref(layout) if layout is not None else None, width, height, input_bitdepth, bitdepth, _vp(out))
     return out
+
+
+def kat_rc_cost(cur, prev, bitdepth):
+    """thor_hip_kat_rc_cost: k_rc_cost on the luma plane `cur` (h x w) after `prev` (None: no previous frame), in the engine's launch sequence.
+    Returns ([sum_intra, sum_best, n_intra], the half-size plane of cur)."""
+    T = _pix(bitdepth)
+    cur = np.ascontiguousarray(cur, dtype=T)
+    h, w = cur.shape
+    if prev is not None:
+        prev = np.ascontiguousarray(prev, dtype=T)
+        assert prev.shape == cur.shape
+    sums = (C.c_ulonglong * 3)()
+    half = np.zeros((h // 2, w // 2), dtype=T)
+    _kat('thor_hip_kat_rc_cost', _vp(cur), _vp(prev) if prev is not None else None, w, h, bitdepth, sums, _vp(half))
+    return [int(v) for v in sums], half

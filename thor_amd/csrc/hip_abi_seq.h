@@ -114,7 +114,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given) return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given || a.rc_given) return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -451,6 +451,35 @@ int thor_hip_stage_frame_scaled(thor_hip_encoder* e, int stream, int slot, const
     } else
       E.eng.stage_scaled_host(frame, v[slot].p);
   });
+  return 0;
+}
+// ---- rate control: tk_rc.h, k_rc_cost ----
+// The caller's structure as an RcConfig; false: refused (a wrong `size` included).  NULL is a config that is off.  Touches no device.
+static bool rc_resolved(const thor_hip_rate_control* rc, RcConfig& c) {
+  if (!rc) { c = RcConfig(); return true; }
+  if (rc->size != (int)sizeof(thor_hip_rate_control)) return false;
+  return rc_resolve(rc->bitrate, rc->buffer_ms, rc->min_qp, rc->max_qp, rc->min_qp_i, rc->max_qp_i, rc->initial_qp, c);
+}
+int thor_hip_rate_control_check(const thor_hip_rate_control* rc) {
+  RcConfig c;
+  return rc_resolved(rc, c) ? 0 : 1;
+}
+int thor_hip_set_rate_control(thor_hip_encoder* e, int stream, const thor_hip_rate_control* rc) {
+  RcConfig c;
+  if (!e || stream < 0 || stream >= e->S || !rc_resolved(rc, c)) return 1;
+  if (!ENC_STREAM(e, stream, log.empty())) return 2;   // in the middle of a sequence
+  ENC_DISPATCH(e, { E.eng.set_rate_control(stream, c); });
+  return 0;
+}
+int thor_hip_get_frame_rc(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_rc* out) {
+  if (!e || stream < 0 || stream >= e->S || !out) return 1;
+  const std::vector<RcStat>& log = ENC_STREAM(e, stream, rclog);
+  if (i < 0 || i >= (int)log.size()) return 1;
+  const RcStat& r = log[i];
+  memset(out, 0, sizeof(*out));
+  out->base_qp = r.base_qp; out->frame_class = r.frame_class;
+  out->sum_intra = r.sum_intra; out->sum_best = r.sum_best; out->n_intra = r.n_intra;
+  out->fullness = r.fullness; out->buffer_bits = r.buffer_bits; out->target_bits = r.target_bits; out->overflows = r.overflows;
   return 0;
 }
 void thor_hip_kernel_time(thor_hip_encoder*, double* sb_ms, long* sb_launches, double* filter_ms) {

@@ -405,6 +405,16 @@ template <typename PIX> void launch_scale_in(const void* frame, const PixLayout&
 template void launch_scale_in<uint8_t>(const void*, const PixLayout&, const ScaleTables&, int, const Plane3<uint8_t>&, int, int, int, int, int);
 template void launch_scale_in<uint16_t>(const void*, const PixLayout&, const ScaleTables&, int, const Plane3<uint16_t>&, int, int, int, int, int);
 
+// The frame analysis of rate control for n streams of one size, on g_stream (tk_encoder.h declares it): one workgroup per tile of the half-size plane.
+template <typename PIX> void launch_rc_cost(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n) {
+  if (n <= 0) return;
+  const int tiles = ((hjobs[0].hw + RC_TILE - 1) / RC_TILE) * ((hjobs[0].hh + RC_TILE - 1) / RC_TILE);
+  hipLaunchKernelGGL(k_rc_cost<PIX>, dim3(tiles, n), dim3(256), 0, g_stream, jobs);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_rc_cost<uint8_t>(const RcJob<uint8_t>*, const RcJob<uint8_t>*, int);
+template void launch_rc_cost<uint16_t>(const RcJob<uint16_t>*, const RcJob<uint16_t>*, int);
+
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {
 // Owning device array of n elements, zeroed (dev_alloc clears), filled from `h` when given; freed with its scope.

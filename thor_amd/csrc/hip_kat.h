@@ -813,6 +813,38 @@ extern "C" int thor_hip_kat_scale_in(const void* src, const thor_hip_scale* scal
   else kat_scale_in<uint16_t>(src, P, w, h, input_bitdepth, bitdepth, (uint16_t*)planar_out);
   return 0;
 }
+// k_rc_cost on host planes, in the engine's sequence for two consecutive frames: `prev` first, without a previous plane, then `cur` against what that wrote.
+template <typename PIX> static void kat_rc_cost(const PIX* cur, const PIX* prev, int w, int h, unsigned long long out[3], PIX* half_out) {
+  const int hw = w / 2, hh = h / 2;
+  const size_t ny = (size_t)w * h, nh = (size_t)hw * hh;
+  DevBuf<PIX> dy(ny), half0(nh), half1(nh);
+  DevBuf<unsigned long long> sums(4);
+  DevBuf<RcJob<PIX>> dj(1);
+  RcJob<PIX> J;
+  J.y = dy.p; J.sy = w; J.hw = hw; J.hh = hh; J.out = sums.p;
+  if (prev) {
+    backend::h2d(dy.p, prev, ny * sizeof(PIX));
+    J.cur = half0.p; J.prev = nullptr;
+    backend::h2d(dj.p, &J, sizeof(J));
+    launch_rc_cost<PIX>(dj.p, &J, 1);
+    backend::dev_sync();
+    backend::dev_memset(sums.p, 0, 4 * sizeof(unsigned long long));
+  }
+  backend::h2d(dy.p, cur, ny * sizeof(PIX));
+  J.cur = half1.p; J.prev = prev ? half0.p : nullptr;
+  backend::h2d(dj.p, &J, sizeof(J));
+  launch_rc_cost<PIX>(dj.p, &J, 1);
+  backend::dev_sync();
+  backend::d2h(out, sums.p, 3 * sizeof(unsigned long long));
+  backend::d2h(half_out, half1.p, nh * sizeof(PIX));
+}
+extern "C" int thor_hip_kat_rc_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3], void* half_out) {
+  if (!cur || !out || !half_out || w % 8 || h % 8 || w < 16 || h < 16 || w > 8192 || h > 8192 || (bitdepth != 8 && bitdepth != 10 && bitdepth != 12)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_rc_cost<uint8_t>((const uint8_t*)cur, (const uint8_t*)prev_or_null, w, h, out, (uint8_t*)half_out);
+  else kat_rc_cost<uint16_t>((const uint16_t*)cur, (const uint16_t*)prev_or_null, w, h, out, (uint16_t*)half_out);
+  return 0;
+}
 // k_rgb_in / k_rgb_out on host buffers, like the two above: the device copy keeps the host pointer's offset from a 16-byte boundary.
 static int kat_rgb_args(const void* rgb, const void* planar, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, RgbFormat& R) {
   auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };

@@ -257,4 +257,58 @@ __global__ __launch_bounds__(256) void k_scale_in(const void* frame, PixLayout L
   }
   scale_vfilter<PIX>(V, t, inter, scale_plane(dst, t.plane), t.plane ? dst.sc : dst.sy, maxv, up, tid, 256);
 }
+
+// ---- rate control: the frame analysis (tk_rc.h: rc_half_sample, rc_block_sum, rc_block_dev, rc_block_inter) --------
+// Streams along y.  One workgroup per tile of RC_TILE x RC_TILE half-size samples (4 x 4 blocks): its 256 lanes make the tile from the staged original
+// (into LDS and into the stream's current half-size plane) and load the previous plane's tile with a halo of RC_RANGE into LDS - samples outside the
+// plane as zeros, which no legal candidate reads.  Then each wavefront takes every fourth block: one lane per sample for the mean and the intra cost,
+// one lane per candidate vector for the inter cost (five rounds of 64 for the 289), DPP reductions; the lanes read neighbouring LDS addresses (the
+// candidates of a round differ in dx) and the block's sample as a broadcast.  The wavefronts' sums meet in LDS: three 64-bit atomic adds per workgroup.
+// Integer sums: the result does not depend on the order.  LDS: 3.3 KiB (8-bit) / 6.6 KiB (16-bit).
+template <typename PIX> __global__ __launch_bounds__(256) void k_rc_cost(const RcJob<PIX>* jobs) {
+  const RcJob<PIX> J = jobs[blockIdx.y];
+  __shared__ PIX s_cur[RC_TILE * RC_TILE];
+  __shared__ PIX s_prev[RC_WIN * RC_WIN];
+  __shared__ unsigned long long s_acc[4][3];
+  const int tid = (int)threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int tiles_x = (J.hw + RC_TILE - 1) / RC_TILE;
+  const int tx0 = ((int)blockIdx.x % tiles_x) * RC_TILE, ty0 = ((int)blockIdx.x / tiles_x) * RC_TILE;
+  for (int i = tid; i < RC_TILE * RC_TILE; i += 256) {
+    const int gx = tx0 + (i & (RC_TILE - 1)), gy = ty0 + i / RC_TILE;
+    PIX v = 0;
+    if (gx < J.hw && gy < J.hh) {
+      v = (PIX)rc_half_sample(J.y, J.sy, gx, gy);
+      J.cur[(size_t)gy * J.hw + gx] = v;
+    }
+    s_cur[i] = v;
+  }
+  if (J.prev)
+    for (int i = tid; i < RC_WIN * RC_WIN; i += 256) {
+      const int gx = tx0 - RC_RANGE + i % RC_WIN, gy = ty0 - RC_RANGE + i / RC_WIN;
+      s_prev[i] = gx >= 0 && gx < J.hw && gy >= 0 && gy < J.hh ? J.prev[(size_t)gy * J.hw + gx] : (PIX)0;
+    }
+  __syncthreads();
+  unsigned long long acc[3] = {0, 0, 0};
+  for (int b = wave; b < (RC_TILE / RC_BLK) * (RC_TILE / RC_BLK); b += 4) {   // b, and with it every branch below, is the same in all lanes of a wavefront
+    const int lx = (b % (RC_TILE / RC_BLK)) * RC_BLK, ly = (b / (RC_TILE / RC_BLK)) * RC_BLK;
+    const int x0 = tx0 + lx, y0 = ty0 + ly;
+    if (x0 >= J.hw || y0 >= J.hh) continue;
+    const int bw = J.hw - x0 < RC_BLK ? J.hw - x0 : RC_BLK, bh = J.hh - y0 < RC_BLK ? J.hh - y0 : RC_BLK, n = bw * bh;
+    const PIX* blk = s_cur + ly * RC_TILE + lx;
+    const unsigned sum = (unsigned)wave_sum_dpp((int)rc_block_sum(blk, RC_TILE, bw, bh, lane, 64));   // at most 64 * 4095: fits the 32-bit reductions
+    const int mean = (int)((sum + (unsigned)(n / 2)) / (unsigned)n);
+    const unsigned intra = (unsigned)wave_sum_dpp((int)rc_block_dev(blk, RC_TILE, bw, bh, mean, lane, 64));
+    unsigned inter = intra;
+    if (J.prev)
+      inter = wave_min_u32_dpp(rc_block_inter(blk, RC_TILE, s_prev + (ly + RC_RANGE) * RC_WIN + lx + RC_RANGE, RC_WIN, bw, bh, x0, y0, J.hw, J.hh, lane, 64));
+    rc_block_add(intra, inter, acc);
+  }
+  if (lane == 0)
+    for (int k = 0; k < 3; k++) s_acc[wave][k] = acc[k];
+  __syncthreads();
+  if (tid < 3) {
+    const unsigned long long v = s_acc[0][tid] + s_acc[1][tid] + s_acc[2][tid] + s_acc[3][tid];
+    if (v) atomicAdd(&J.out[tid], v);
+  }
+}
 }  // namespace tk

@@ -30,6 +30,10 @@ struct CliArgs {
   int scale_filter = 1;      // -scale_filter bilinear|bicubic
   int scale_site = 1;        // -scale_site left|centre
   bool scale_given = false;  // one of the four was given: front-end options like -pixfmt
+  // -rc_bitrate N [-rc_buffer_ms -rc_min_qp -rc_max_qp -rc_min_qpI -rc_max_qpI -rc_initial_qp]: the library's rate control (tk_rc.h), the same target for every
+  // stream.  Not options of the reference: its -bitrate / -max_qp ... keep their handling below.
+  int rc[7] = {0, 0, 0, 0, 0, 0, 0};  // bitrate, buffer_ms, min_qp, max_qp, min_qp_i, max_qp_i, initial_qp
+  bool rc_given = false;     // one of the seven was given: front-end options like -pixfmt
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -89,6 +93,17 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
       else if (k == "-scale_filter") { a.scale_filter = v == "bicubic"; ok = v == "bicubic" || v == "bilinear"; }
       else { a.scale_site = v == "left"; ok = v == "left" || v == "centre"; }
       if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
+    else if (k.compare(0, 4, "-rc_") == 0) {
+      static const char* const names[7] = {"-rc_bitrate", "-rc_buffer_ms", "-rc_min_qp", "-rc_max_qp", "-rc_min_qpI", "-rc_max_qpI", "-rc_initial_qp"};
+      int which = -1;
+      for (int j = 0; j < 7; j++) if (k == names[j]) which = j;
+      if (which < 0) { if (a.unknown.empty()) a.unknown = k; }
+      else {
+        a.rc_given = true;
+        a.rc[which] = I();
+        if ((a.rc[which] < 0 || (which >= 2 && a.rc[which] > 51)) && a.unsupported.empty()) a.unsupported = k + " " + v;   // the set as a whole: cli_parse
+      }
     }
     else if (k == "-width") p.width = I();
     else if (k == "-height") p.height = I();
@@ -174,6 +189,8 @@ static inline CliArgs cli_parse(int argc, char** argv) {
   cli_apply(a, rest);
   if (!a.unknown.empty()) { fprintf(stderr, "Run-time error...\nunknown option %s\n...now exiting to system...\n", a.unknown.c_str()); exit(2); }
   if (!a.unsupported.empty()) { fprintf(stderr, "Run-time error...\noption %s is not implemented by this path (it changes the bitstream)\n...now exiting to system...\n", a.unsupported.c_str()); exit(2); }
+  RcConfig rcc;
+  if (a.rc_given && !rc_resolve(a.rc[0], a.rc[1], a.rc[2], a.rc[3], a.rc[4], a.rc[5], a.rc[6], rcc)) { fprintf(stderr, "Run-time error...\nthe -rc_ options do not describe a rate control (a minimum above its maximum)\n...now exiting to system...\n"); exit(2); }
   return a;
 }
 
@@ -232,6 +249,14 @@ template <typename PIX> int cli_run(const CliArgs& a) {
   fseek(fi, 0, SEEK_END);
   const int file_frames = (int)(ftell(fi) / (long)fsz);
   for (int s = 0; s < a.streams; s++) eng.begin_sequence(s, a.skip + s * a.num_frames, a.num_frames, file_frames);
+  RcConfig rcc;
+  if (a.rc_given && rc_resolve(a.rc[0], a.rc[1], a.rc[2], a.rc[3], a.rc[4], a.rc[5], a.rc[6], rcc) && rcc.on())
+    for (int s = 0; s < a.streams; s++) {
+      RcConfig c = rcc;
+      // THOR_RC_SCALE=k (tests): stream s aims at (1 + k * s) times the bitrate, so that one engine holds streams with different targets
+      if (const char* sc = getenv("THOR_RC_SCALE")) c.bitrate = (int)((long long)c.bitrate * (1 + atoi(sc) * s));
+      eng.set_rate_control(s, c);
+    }
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
   auto upload = [&](int s) { if (use_scale) eng.stage_scaled_host(frame.data(), eng.st[s].orig.p); else if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
   auto download = [&](int s) { if (use_rgb) eng.fetch_rgb_host(eng.st[s].rec.p, rec.data(), rgb); else if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
@@ -302,6 +327,18 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       fwrite(eng.st[s].out.data(), 1, eng.st[s].out.size(), fo);
       fclose(fo);
     }
+  }
+  if (const char* rlp = getenv("THOR_RC_LOG")) {   // tests: the controller's log, one line per coded frame of every rate-controlled stream
+    FILE* fl = fopen(rlp, "w");
+    if (!fl) { fprintf(stderr, "cannot open %s\n", rlp); return 5; }
+    for (int s = 0; s < a.streams; s++)
+      for (size_t i = 0; i < eng.st[s].rclog.size(); i++) {
+        const RcStat& r = eng.st[s].rclog[i];
+        const FrameStat& f = eng.st[s].log[i];
+        fprintf(fl, "%d %d %d %d %d %d %d %d %llu %llu %llu %lld %d\n", s, f.display, f.frame_type, r.frame_class, r.qp_rule, r.base_qp, f.qp, f.num_bits, r.sum_intra, r.sum_best, r.n_intra,
+                r.fullness, r.overflows);
+      }
+    fclose(fl);
   }
   for (int s = 0; s < a.streams; s++) {
     if (a.streams > 1) printf("stream %d\n", s);

@@ -20,6 +20,7 @@
 #include "tk_clpf.h"
 #include "tk_filters.h"
 #include "tk_scale.h"
+#include "tk_rc.h"
 #include "tk_report.h"
 
 namespace tk {
@@ -80,6 +81,8 @@ template <typename PIX> void launch_rgb_out(const Plane3<PIX>& src, void* frame,
 // A frame of another size (tk_scale.h: ScalePlan, k_scale_in) -> planes at the engine's depth, one launch on the library's stream.
 template <typename PIX> void launch_scale_in(const void* frame, const PixLayout& L, const ScaleTables& tab, int vrows, const Plane3<PIX>& dst, int src_w, int width,
                                              int height, int bitdepth, int input_bitdepth);
+// The frame analysis of rate control (tk_rc.h, k_rc_cost) of n streams, one launch on the library's stream.  jobs / hjobs: device / host arrays of n RcJob.
+template <typename PIX> void launch_rc_cost(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -105,7 +108,9 @@ struct FrameParams {
   int interp_src[2] = {0, 0};              // window indices the interpolated frame is built from (before pruning)
   double lambda_coeff = 1.0;
   int b_level = 0;
+  int qp_rule = 0;                         // QR_*: how qp follows from the base QP (GopScheduler::rule_qp)
 };
+enum { QR_BASE = 0, QR_I, QR_P, QR_B0, QR_B1, QR_B2, QR_B3, QR_B };
 
 // Coding-order schedule of one stream: a resumable restatement of the frame loop of enc/mainenc.c:246-625
 // (frame types, QPs, b_level, reference lists for low-delay and dyadic hierarchical-B GOPs, the fall-back
@@ -135,6 +140,19 @@ struct GopScheduler {
     min_interp_depth = ilog2i((unsigned)(p.num_reorder_pics + 1)) - 3;
     if (p.frame_rate > 30) min_interp_depth--;
     frame_num0 = skip; k = 0; num_encoded = 0; last_intra = 0; last_PorI = -1; started = true;
+  }
+  // The QP of a frame from the base QP (mainenc.c:281-314): which of the dqp / mqp pairs applies is the frame's qp_rule, set by next(); the base is the
+  // parameter set's qp, or the rate control's choice for the frame (Engine::rate_control).
+  static int rule_qp(const SeqParams& p, int rule, int base) {
+    int q = base;
+    if (rule == QR_I) q = base + p.dqpI;
+    else if (rule == QR_P) q = (int)(p.mqpP * (float)base) + p.dqpP;
+    else if (rule == QR_B0) q = (int)(p.mqpB0 * (float)base) + p.dqpB0;
+    else if (rule == QR_B1) q = (int)(p.mqpB1 * (float)base) + p.dqpB1;
+    else if (rule == QR_B2) q = (int)(p.mqpB2 * (float)base) + p.dqpB2;
+    else if (rule == QR_B3) q = (int)(p.mqpB3 * (float)base) + p.dqpB3;
+    else if (rule == QR_B) q = (int)(p.mqpB * (float)base) + p.dqpB;
+    return q < 0 ? 0 : (q > 51 ? 51 : q);
   }
   // ring_frame_num(idx): frame_num of the reconstruction currently at sliding-window position idx.
   // Returns false when the sequence is finished; otherwise fills f and the absolute input frame index.
@@ -170,23 +188,11 @@ struct GopScheduler {
       const int coded_phase = (num_encoded + sub_gop - 2) % sub_gop + 1;
       const int b_level = ilog2i((unsigned)coded_phase);
       f.b_level = b_level;
-      if (f.frame_type == F_I) { f.qp = sp.qp + sp.dqpI; last_intra = f.frame_num; }
-      else if (sp.num_reorder_pics == 0) {
-        if (num_encoded % sp.HQperiod) f.qp = (int)(sp.mqpP * (float)sp.qp) + sp.dqpP; else f.qp = sp.qp;
-      } else {
-        if (f.frame_num % sub_gop) {
-          if (dyadic) {
-            if (b_level == 0) f.qp = (int)(sp.mqpB0 * (float)sp.qp) + sp.dqpB0;
-            else if (b_level == 1) f.qp = (int)(sp.mqpB1 * (float)sp.qp) + sp.dqpB1;
-            else if (b_level == 2) f.qp = (int)(sp.mqpB2 * (float)sp.qp) + sp.dqpB2;
-            else if (b_level == 3) f.qp = (int)(sp.mqpB3 * (float)sp.qp) + sp.dqpB3;
-            else f.qp = (int)(sp.mqpB * (float)sp.qp) + sp.dqpB;
-          } else f.qp = (int)(sp.mqpB * (float)sp.qp) + sp.dqpB;
-        } else {
-          if (f.frame_num % sp.HQperiod) f.qp = (int)(sp.mqpP * (float)sp.qp) + sp.dqpP; else f.qp = sp.qp;
-        }
-      }
-      f.qp = f.qp < 0 ? 0 : (f.qp > 51 ? 51 : f.qp);
+      if (f.frame_type == F_I) { f.qp_rule = QR_I; last_intra = f.frame_num; }
+      else if (sp.num_reorder_pics == 0) f.qp_rule = (num_encoded % sp.HQperiod) ? QR_P : QR_BASE;
+      else if (f.frame_num % sub_gop) f.qp_rule = !dyadic ? QR_B : b_level == 0 ? QR_B0 : b_level == 1 ? QR_B1 : b_level == 2 ? QR_B2 : b_level == 3 ? QR_B3 : QR_B;
+      else f.qp_rule = (f.frame_num % sp.HQperiod) ? QR_P : QR_BASE;
+      f.qp = rule_qp(sp, f.qp_rule, sp.qp);
       f.num_ref = f.frame_type == F_I ? 0 : (num_encoded < sp.max_num_ref ? num_encoded : sp.max_num_ref);
       f.interp_ref = 0;
       int ra[kMaxRefs + 2] = {0, 0, 0, 0, 0, 0};
@@ -381,6 +387,14 @@ template <typename PIX> struct Stream {
   std::vector<uint8_t> out;  // finished stream bytes (4-byte big-endian length + payload per frame)
   int sh_bits = 0;           // bits of the sequence header
   std::vector<FrameStat> log;  // one record per coded frame, in coding order (cleared by begin_sequence)
+  // rate control (tk_rc.h; off unless Engine::set_rate_control turned it on): nothing below is allocated or touched while it is off
+  RcConfig rc;
+  RcState rcs;
+  PIX* rc_half[2] = {nullptr, nullptr};  // the half-size luma of the frame analysed last and of the one before: they alternate
+  int rc_flip = 0;                       // the plane the next analysis writes
+  bool rc_prev = false;                  // the other plane holds the previous frame of this sequence
+  RcStat rc_cur;                         // the frame in flight: the decision and its analysis sums
+  std::vector<RcStat> rclog;             // one record per coded frame, like `log`
 };
 
 // The caller-visible fields of the reference's deblock_data_t (common/types.h:178-187) in declaration order, from one DbCell:
@@ -431,6 +445,8 @@ template <typename PIX> class Engine {
   void* d_scale = nullptr;
   ScaleTables scale_tab;
   bool scale_dirty = true;
+  RcJob<PIX>* d_rcjobs = nullptr;         // rate control: the analysis jobs and, per stream, four slots for the three sums (allocated on first use)
+  unsigned long long* d_rcsums = nullptr;
 
   // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
   int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
@@ -520,6 +536,7 @@ template <typename PIX> class Engine {
   size_t clpf_stat_words() const { return 4 * ((size_t)(sp.width / 8) * (sp.height / 8) + 2 * (size_t)(sp.width / 16) * (sp.height / 16)); }
   void close() {
     for (auto& s : st) {
+      backend::dev_free(s.rc_half[0]); backend::dev_free(s.rc_half[1]);
       backend::dev_free(s.clpf_stats); backend::dev_free(s.clpf_fb_on);
       s.orig.release(); s.rec.release(); s.tmp.release(); s.interp.release();
       backend::dev_free(s.cdef_dir); backend::dev_free(s.cdef_var); backend::dev_free(s.cdef_fbc); backend::dev_free(s.cdef_mse);
@@ -545,6 +562,8 @@ template <typename PIX> class Engine {
     backend::dev_free(d_packed); d_packed = nullptr;
     backend::dev_free(d_layout); d_layout = nullptr; d_layout_bytes = 0;
     backend::dev_free(d_scale); d_scale = nullptr; scale_dirty = true;
+    backend::dev_free(d_rcjobs); d_rcjobs = nullptr;
+    backend::dev_free(d_rcsums); d_rcsums = nullptr;
   }
 
   // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
@@ -755,7 +774,71 @@ template <typename PIX> class Engine {
 
   // Coding-order schedule.  begin_sequence fixes the chunk [skip, skip+num_frames) of an input holding
   // file_frames frames (needed for the reference's end-of-sequence behaviour with reordered GOPs).
-  void begin_sequence(int s, int skip, int num_frames, int file_frames) { st[s].gop.init(sp, skip, num_frames, file_frames); st[s].log.clear(); }
+  void begin_sequence(int s, int skip, int num_frames, int file_frames) {
+    st[s].gop.init(sp, skip, num_frames, file_frames); st[s].log.clear();
+    if (st[s].rc.on()) set_rate_control(s, st[s].rc);   // the target stays, the controller starts again
+  }
+  // Rate control of stream s from its next frame on (tk_rc.h; c.on() false: off).  Legal while the stream's log is empty: before its first frame or right
+  // after begin_sequence - the caller checks.  The controller starts empty and the next analysis has no previous frame.
+  void set_rate_control(int s, const RcConfig& c) {
+    Stream<PIX>& q = st[s];
+    q.rc = c;
+    if (q.rc.on() && q.rc.initial_qp == 0) q.rc.initial_qp = sp.qp;
+    q.rcs.begin(q.rc, sp.frame_rate);
+    q.rc_prev = false;
+    q.rclog.clear();
+  }
+  // The base QP of the frames fp[s] of the rate-controlled streams in [first, first + count), origs in place: one analysis launch for all of them, the
+  // three sums of each back to the host, the controller's decision, and the frame's QP from it by the rule the schedule gave the frame.
+  void rate_control(std::vector<FrameParams>& fp, int first, int count) {
+    std::vector<RcJob<PIX>> hj;
+    std::vector<int> who;
+    const int hw = sp.width / 2, hh = sp.height / 2;
+    if (!d_rcsums) {
+      d_rcsums = (unsigned long long*)backend::dev_alloc((size_t)S * 4 * sizeof(unsigned long long));
+      d_rcjobs = (RcJob<PIX>*)backend::dev_alloc((size_t)S * sizeof(RcJob<PIX>));
+    }
+    for (int s = first; s < first + count; s++) {
+      Stream<PIX>& q = st[s];
+      if (!q.rc.on()) continue;
+      for (int k = 0; k < 2; k++)
+        if (!q.rc_half[k]) q.rc_half[k] = (PIX*)backend::dev_alloc((size_t)hw * hh * sizeof(PIX));
+      RcJob<PIX> J;
+      J.y = q.orig.p.y; J.sy = q.orig.p.sy; J.hw = hw; J.hh = hh;
+      J.cur = q.rc_half[q.rc_flip]; J.prev = q.rc_prev ? q.rc_half[q.rc_flip ^ 1] : nullptr;
+      J.out = d_rcsums + (size_t)s * 4;
+      hj.push_back(J);
+      who.push_back(s);
+    }
+    const int n = (int)who.size();
+    backend::dev_memset(d_rcsums + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long));
+#if TK_HOST
+    for (int k = 0; k < n; k++) rc_cost_frame(hj[k]);
+#else
+    backend::h2d(d_rcjobs, hj.data(), (size_t)n * sizeof(RcJob<PIX>));
+    launch_rc_cost<PIX>(d_rcjobs, hj.data(), n);
+#endif
+    backend::dev_sync();
+    std::vector<unsigned long long> sums((size_t)count * 4);
+    backend::d2h(sums.data(), d_rcsums + (size_t)first * 4, sums.size() * sizeof(unsigned long long));
+    for (int k = 0; k < n; k++) {
+      const int s = who[k];
+      Stream<PIX>& q = st[s];
+      FrameParams& f = fp[s];
+      q.rc_flip ^= 1;
+      q.rc_prev = true;
+      RcStat& r = q.rc_cur;
+      r = RcStat();
+      r.frame_class = rc_class(f.frame_type, f.b_level);
+      r.qp_rule = f.qp_rule;
+      r.sum_intra = sums[(size_t)(s - first) * 4]; r.sum_best = sums[(size_t)(s - first) * 4 + 1]; r.n_intra = sums[(size_t)(s - first) * 4 + 2];
+      int fq[52];
+      for (int b = 0; b < 52; b++) fq[b] = GopScheduler::rule_qp(sp, f.qp_rule, b);
+      r.base_qp = rc_decide(q.rc, q.rcs, r.frame_class, (long long)(r.frame_class == 0 ? r.sum_intra : r.sum_best), fq);
+      f.qp = fq[r.base_qp];
+      q.cur.qp = f.qp;
+    }
+  }
   // Next frame to code for stream s: fills st[s].cur / st[s].cur_abs; false when the chunk is finished.
   bool schedule(int s) {
     Stream<PIX>& q = st[s];
@@ -808,7 +891,7 @@ template <typename PIX> class Engine {
   }
 
   // Encode one frame per stream (origs already uploaded). Appends to st[s].out.
-  void encode_frames(const std::vector<FrameParams>& fp) {
+  void encode_frames(std::vector<FrameParams>& fp) {
     prepare_jobs(fp, 0, S);
     backend::run_superblocks<PIX>(d_jobs, h_jobs.data(), S, nullptr);
     finish_frames(fp, 0, S);
@@ -867,7 +950,10 @@ template <typename PIX> class Engine {
   }
 
   // Frame jobs of streams [first, first + count) for the frames fp[s] (origs in place): interpolated references, FrameJob set-up, upload.
-  void prepare_jobs(const std::vector<FrameParams>& fp, int first, int count) {
+  // With rate control on for one of them the frames' QPs are chosen here (rate_control), which is why fp is not const.
+  void prepare_jobs(std::vector<FrameParams>& fp, int first, int count) {
+    for (int s = first; s < first + count; s++)
+      if (st[s].rc.on()) { rate_control(fp, first, count); break; }
     if (!external_interp) make_interp_frames(fp, first, count);
     for (int s = first; s < first + count; s++) {
       Stream<PIX>& q = st[s];
@@ -1085,6 +1171,12 @@ template <typename PIX> class Engine {
       if (sp.clpf)
         for (auto& pr : lplan[s].bits) b.put(pr.first, pr.second);
       q.log.back().num_bits += b.nbits;
+      if (q.rc.on()) {  // the controller learns the frame's bits before the stream's next frame is prepared
+        RcStat& r = q.rc_cur;
+        rc_update(q.rcs, r.frame_class, (long long)(r.frame_class == 0 ? r.sum_intra : r.sum_best), f.qp, q.log.back().num_bits);
+        r.fullness = q.rcs.F; r.buffer_bits = q.rcs.B; r.target_bits = q.rcs.T; r.overflows = q.rcs.overflows;
+        q.rclog.push_back(r);
+      }
       q.num_encoded++;
       if (q.gop.started) q.gop.advance(f);
       if (raw_frames) continue;

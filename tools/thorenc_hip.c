@@ -4,6 +4,7 @@
  *               [-of str.bit] [-rf rec.yuv] [-streams S] [-snrcalc 0|1] [-stat file] [-pixfmt i420|nv12|nv21|p010|rgba|bgra|rgb24|bgr24] [-name value ...]
  *               [-rgbmatrix 601|709|2020] [-rgbrange limited|full] [-rgbsite centre|left]
  *               [-src_width W -src_height H] [-scale_filter bilinear|bicubic] [-scale_site left|centre]
+ *               [-rc_bitrate N] [-rc_buffer_ms M] [-rc_min_qp Q -rc_max_qp Q] [-rc_min_qpI Q -rc_max_qpI Q] [-rc_initial_qp Q]
  * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
  * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
  * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
@@ -12,6 +13,8 @@
  * -rgbsite (left).
  * -src_width / -src_height: the -if frames have that size (in the -pixfmt layout, which must not be RGB) and are resampled to -width x -height on
  * the device while they are staged (thor_hip_stage_frame_scaled; defaults bicubic, left); -rf stays at the coded size.
+ * -rc_bitrate N: the library's rate control (thor_hip_set_rate_control) at N bits per second, the same target for every stream; the other -rc_ options are
+ * the fields of thor_hip_rate_control.  They are not the reference's -bitrate / -max_qp ..., which stay refused.
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -55,6 +58,7 @@ int main(int argc, char** argv) {
   const char *rgbmatrix = "709", *rgbrange = "limited", *rgbsite = "left";
   const char *scalefilter = "bicubic", *scalesite = "left";
   int src_w = 0, src_h = 0, scaled = 0;
+  thor_hip_rate_control rc = {sizeof(thor_hip_rate_control), 0, 0, 0, 0, 0, 0, 0};
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -79,6 +83,13 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-src_height")) { src_h = atoi(v); scaled = 1; }
     else if (!strcmp(k, "-scale_filter")) { scalefilter = v; scaled = 1; }
     else if (!strcmp(k, "-scale_site")) { scalesite = v; scaled = 1; }
+    else if (!strcmp(k, "-rc_bitrate")) rc.bitrate = atoi(v);
+    else if (!strcmp(k, "-rc_buffer_ms")) rc.buffer_ms = atoi(v);
+    else if (!strcmp(k, "-rc_min_qp")) rc.min_qp = atoi(v);
+    else if (!strcmp(k, "-rc_max_qp")) rc.max_qp = atoi(v);
+    else if (!strcmp(k, "-rc_min_qpI")) rc.min_qp_i = atoi(v);
+    else if (!strcmp(k, "-rc_max_qpI")) rc.max_qp_i = atoi(v);
+    else if (!strcmp(k, "-rc_initial_qp")) rc.initial_qp = atoi(v);
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -110,6 +121,7 @@ int main(int argc, char** argv) {
                           !strcmp(scalesite, "left") ? 1 : !strcmp(scalesite, "centre") ? 0 : -1};
   if (scaled && (scale.filter < 0 || scale.chroma_site < 0)) { fprintf(stderr, "Run-time error...\noption -scale_filter %s -scale_site %s is unknown\n...now exiting to system...\n", scalefilter, scalesite); return 2; }
   if (scaled && (rgb || !thor_hip_scale_bytes_for(p.width, p.height, p.input_bitdepth, &scale, lay))) { fprintf(stderr, "Run-time error...\n-src_width %d -src_height %d with -pixfmt %s cannot be resampled to %dx%d\n...now exiting to system...\n", scale.src_width, scale.src_height, pixfmt, p.width, p.height); return 2; }
+  if (thor_hip_rate_control_check(&rc)) { fprintf(stderr, "Run-time error...\nthe -rc_ options do not describe a rate control (a negative value, a minimum above its maximum, a QP above 51)\n...now exiting to system...\n"); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
   size_t fsz = rgb ? thor_hip_rgb_bytes(e, rgb) : thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth, or RGB frames */
@@ -135,6 +147,8 @@ int main(int argc, char** argv) {
   long file_frames = wrap > 0 ? (long)skip + (long)S * n : (long)(ftell(fi) / (long)isz);
   for (int s = 0; s < S; s++)
     if (thor_hip_begin_sequence(e, s, skip + s * n, n, (int)file_frames)) { fprintf(stderr, "bad sequence bounds\n"); return 5; }
+  for (int s = 0; s < S && rc.bitrate; s++)
+    if (thor_hip_set_rate_control(e, s, &rc)) { fprintf(stderr, "rate control refused\n"); return 5; }
   unsigned char** recs = (unsigned char**)calloc((size_t)S * n, sizeof(unsigned char*));
   double t0 = now_s(), tenc = 0;
   int coded = 0;
