@@ -341,6 +341,52 @@ typedef struct thor_hip_frame_rc {
 /* Record i (coding order, the index of thor_hip_get_frame_stats) of a rate-controlled stream.  Returns 0; 1 on a bad argument or a stream without rate control. */
 int thor_hip_get_frame_rc(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_rc* out);
 
+/* Key frames: where a stream may be entered.  Low-delay parameter sets only (num_reorder_pics == 0): for a hierarchical-B set every entry point below returns 2
+ * and touches nothing.  A promoted frame is exactly the I frame -intra_period would have made at its place (frame type I, the I rule of qp(b), no references,
+ * lambda_coeffI, the I frame's number of intra modes) and later frames drop every reference older than it; nothing else of the schedule moves - the coded-frame
+ * count, the HQperiod phase of later frames and the distance to the last P or I frame run on.  So -intra_period 0 with key frames asked for at 0, 4, 8 ... is
+ * byte for byte the stream of -intra_period 4.
+ *
+ * thor_hip_force_key_frame: frame display_index of the stream's chunk (what thor_hip_next_frame reports; for low delay the coded index) becomes a key frame.  The
+ * frame must not be coded yet - one that thor_hip_next_frame has already handed out still qualifies.  Up to 64 requests may be pending per stream; a frame asked
+ * for twice counts once, a request leaves the set when its frame is scheduled, thor_hip_begin_sequence empties the set.  A request for a frame the schedule makes
+ * an I frame anyway is accepted and changes nothing.  Returns 0; 1: bad argument, a frame outside the chunk or already coded, a full set; 2: not low delay. */
+int thor_hip_force_key_frame(thor_hip_encoder* e, int stream, int display_index);
+/* Scene cuts, per stream.  The analysis is the one of rate control above (k_rc_cost, the same two half-size planes per stream): a stream with scene cuts on is
+ * analysed before each of its frames whether it is rate-controlled or not, I frames included, so that the next frame has its predecessor.  Normative, integers
+ * only: a P frame of the stream is promoted if and only if
+ *   its analysis had a previous plane (not the first frame after thor_hip_begin_sequence, thor_hip_set_rate_control or thor_hip_set_scene_cut),
+ *   frame_num - last_intra >= max(1, min_interval)                      (last_intra: the frame number of the stream's last I frame of any origin), and
+ *   sum_intra > 0 and sum_best * 100 >= (unsigned long long)percent * sum_intra.
+ * The sums are below 2^36 (an 8192 x 8192 frame of 12-bit samples: 2^24 half-size samples of at most 2^12 each) and percent <= 100 < 2^7: both products stay
+ * below 2^43.  Per stream the order is analysis, cut decision and promotion, and only then the rate controller's decision: a promoted frame is class 0 there
+ * (cost sum_intra, budget 4 T, the I range of base QPs) and updates f[0], a[0], n[0].  tests/key_model.py restates the rule.
+ * There is no default for percent: what separates a cut from motion depends on the content. */
+typedef struct thor_hip_scene_cut {
+  int size;           /* sizeof(thor_hip_scene_cut) */
+  int percent;        /* 1 .. 100; 0 = off */
+  int min_interval;   /* >= 0: frames since the last I frame before a cut may be declared (0 acts as 1) */
+} thor_hip_scene_cut;
+/* 0 when thor_hip_set_scene_cut would accept *sc (NULL included: off); 1 otherwise: `size` is wrong, percent outside 0 .. 100, min_interval negative.  Needs no
+ * encoder and no device. */
+int thor_hip_scene_cut_check(const thor_hip_scene_cut* sc);
+/* Legal where thor_hip_set_rate_control is: before the stream's first frame and right after thor_hip_begin_sequence, which keeps the setting.  Returns 0; 1 for
+ * a bad argument or a refused *sc; 2 in the middle of a sequence or when the parameter set is not low delay.  While no request is pending and scene cuts are off
+ * for every stream the encoder launches, copies, allocates and synchronises exactly as before. */
+int thor_hip_set_scene_cut(thor_hip_encoder* e, int stream, const thor_hip_scene_cut* sc);
+/* The analysis as a call of its own, for a caller that keeps the rungs of a ladder aligned: analyse one rung, apply the rule above, and call
+ * thor_hip_force_key_frame on every rung.  sums = sum_intra, sum_best, n_intra of the STAGED original in `slot` against the one in prev_slot (-1: no
+ * predecessor, inter = intra) - bit for bit what the stream's own analysis finds for the same two frames.  The kernel's second instantiation halves the
+ * previous original while it loads it: neither the stream's two half-size planes nor its controller are touched, and the call may come at any time between
+ * encode calls.  Returns 0; 1: bad argument or a slot that is not staged; 2: not low delay. */
+int thor_hip_scene_cost(thor_hip_encoder* e, int stream, int slot, int prev_slot, unsigned long long sums[3]);
+typedef struct thor_hip_frame_key {
+  int reason;                      /* 0: the schedule's own frame type; 1: a forced key frame; 2: a scene cut.  1 when both apply */
+  unsigned long long sum_intra, sum_best, n_intra;   /* the frame's analysis; zero when the frame was not analysed */
+} thor_hip_frame_key;
+/* Record i (coding order, the index of thor_hip_get_frame_stats) of a stream.  Returns 0; 1 on a bad argument. */
+int thor_hip_get_frame_key(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_key* out);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -569,6 +615,9 @@ int thor_hip_kat_scale_in(const void* src, const thor_hip_scale* scale, const th
  * for bitdepth 8, uint16_t for 10 / 12); w, h: multiples of 8, at least 16.  out: sum_intra, sum_best, n_intra of `cur`; half_out: its half-size plane, w / 2 x
  * h / 2 samples of the same type.  Returns 0, 1 = bad argument, 3 = no device. */
 int thor_hip_kat_rc_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3], void* half_out);
+/* The kernel's other instantiation, the one behind thor_hip_scene_cost: one launch on `cur` with `prev_or_null` as a full-size original that the kernel halves
+ * while it loads it.  The planes are copied into device frames whose rows start 16-byte aligned, as staged frames do.  Same arguments and return values. */
+int thor_hip_kat_scene_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3]);
 /* The same for k_rgb_in / k_rgb_out: `src` / `dst` hold thor_hip_rgb_bytes_for(w, h, fmt) bytes in `fmt` (dst: plus 64 guard bytes, all of it uploaded
  * before the kernel runs and downloaded afterwards); the planar frames are at `bitdepth` (k_rgb_out rounds back to input_bitdepth first).  Any depth
  * of `fmt` goes with any input_bitdepth <= bitdepth.  Same return values. */

@@ -168,6 +168,24 @@ class FrameRc(C.Structure):
                 ('fullness', C.c_longlong), ('buffer_bits', C.c_longlong), ('target_bits', C.c_longlong), ('overflows', C.c_int)]
 
 
+class SceneCut(C.Structure):
+    """thor_hip_scene_cut (include/thor_hip.h): a P frame whose sum_best reaches `percent` per cent of its sum_intra, at least max(1, min_interval) frames
+    after the stream's last I frame, becomes a key frame.  percent has no default; 0 is off."""
+    _fields_ = [('size', C.c_int), ('percent', C.c_int), ('min_interval', C.c_int)]
+
+    def __init__(self, percent=0, min_interval=0):
+        super().__init__(C.sizeof(SceneCut), percent, min_interval)
+
+    def ok(self):
+        """thor_hip_scene_cut_check: would thor_hip_set_scene_cut accept it?  Needs no device."""
+        return lib().thor_hip_scene_cut_check(C.byref(self)) == 0
+
+
+class FrameKey(C.Structure):
+    """thor_hip_frame_key (include/thor_hip.h): why a coded frame is a key frame, and its analysis sums."""
+    _fields_ = [('reason', C.c_int), ('sum_intra', C.c_ulonglong), ('sum_best', C.c_ulonglong), ('n_intra', C.c_ulonglong)]
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -238,6 +256,12 @@ def lib():
         L.thor_hip_set_rate_control.argtypes = [C.c_void_p, C.c_int, C.POINTER(RateControl)]
         L.thor_hip_get_frame_rc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameRc)]
         L.thor_hip_kat_rc_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.c_void_p]
+        L.thor_hip_kat_scene_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
+        L.thor_hip_force_key_frame.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.thor_hip_scene_cut_check.argtypes = [C.POINTER(SceneCut)]
+        L.thor_hip_set_scene_cut.argtypes = [C.c_void_p, C.c_int, C.POINTER(SceneCut)]
+        L.thor_hip_scene_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
+        L.thor_hip_get_frame_key.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameKey)]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -520,6 +544,35 @@ class Encoder:
                         'n_intra': int(f.n_intra), 'fullness': int(f.fullness), 'buffer_bits': int(f.buffer_bits), 'target_bits': int(f.target_bits),
                         'overflows': f.overflows})
         return out
+
+    def force_key_frame(self, stream, index):
+        """A key frame at chunk-relative frame `index` of a low-delay stream (thor_hip_force_key_frame); raises ValueError when the library refuses."""
+        r = lib().thor_hip_force_key_frame(self.h, stream, index)
+        if r:
+            raise ValueError('key frame refused: ' + ('the parameter set is not low delay' if r == 2 else 'bad stream, a frame already coded or too many requests'))
+
+    def set_scene_cut(self, stream, sc):
+        """Scene cuts of one stream (a SceneCut; None or percent 0: off): thor_hip_set_scene_cut.  Legal where set_rate_control is."""
+        r = lib().thor_hip_set_scene_cut(self.h, stream, C.byref(sc) if sc is not None else None)
+        if r:
+            raise ValueError('scene cut refused: ' + ('the stream is in the middle of a sequence or not low delay' if r == 2 else 'bad stream or values'))
+
+    def frame_key(self, stream):
+        """Per coded frame, index for index with frame_stats: dict(reason, sum_intra, sum_best, n_intra) (thor_hip_get_frame_key)."""
+        L, out, f = lib(), [], FrameKey()
+        for i in range(L.thor_hip_frame_stats_count(self.h, stream)):
+            if L.thor_hip_get_frame_key(self.h, stream, i, C.byref(f)):
+                break
+            out.append({'reason': f.reason, 'sum_intra': int(f.sum_intra), 'sum_best': int(f.sum_best), 'n_intra': int(f.n_intra)})
+        return out
+
+    def scene_cost(self, stream, slot, prev_slot=-1):
+        """[sum_intra, sum_best, n_intra] of the staged frame `slot` against the staged frame prev_slot (-1: none): thor_hip_scene_cost."""
+        sums = (C.c_ulonglong * 3)()
+        r = lib().thor_hip_scene_cost(self.h, stream, slot, prev_slot, sums)
+        if r:
+            raise ValueError('scene cost refused: ' + ('the parameter set is not low delay' if r == 2 else 'bad stream or a slot that is not staged'))
+        return [int(v) for v in sums]
 
     def report(self, stream):
         """The reference encoder's stdout report for the stream so far (thor_hip_report)."""
@@ -969,3 +1022,17 @@ def kat_rc_cost(cur, prev, bitdepth):
     half = np.zeros((h // 2, w // 2), dtype=T)
     _kat('thor_hip_kat_rc_cost', _vp(cur), _vp(prev) if prev is not None else None, w, h, bitdepth, sums, _vp(half))
     return [int(v) for v in sums], half
+
+
+def kat_scene_cost(cur, prev, bitdepth):
+    """thor_hip_kat_scene_cost: the instantiation of k_rc_cost behind thor_hip_scene_cost on the luma plane `cur` (h x w) against the ORIGINAL `prev`
+    (None: no previous frame).  Returns [sum_intra, sum_best, n_intra]."""
+    T = _pix(bitdepth)
+    cur = np.ascontiguousarray(cur, dtype=T)
+    h, w = cur.shape
+    if prev is not None:
+        prev = np.ascontiguousarray(prev, dtype=T)
+        assert prev.shape == cur.shape
+    sums = (C.c_ulonglong * 3)()
+    _kat('thor_hip_kat_scene_cost', _vp(cur), _vp(prev) if prev is not None else None, w, h, bitdepth, sums)
+    return [int(v) for v in sums]

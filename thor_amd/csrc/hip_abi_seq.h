@@ -114,7 +114,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given || a.rc_given) return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given || a.rc_given || a.key_given) return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -480,6 +480,55 @@ int thor_hip_get_frame_rc(const thor_hip_encoder* e, int stream, int i, thor_hip
   out->base_qp = r.base_qp; out->frame_class = r.frame_class;
   out->sum_intra = r.sum_intra; out->sum_best = r.sum_best; out->n_intra = r.n_intra;
   out->fullness = r.fullness; out->buffer_bits = r.buffer_bits; out->target_bits = r.target_bits; out->overflows = r.overflows;
+  return 0;
+}
+// ---- key frames: GopScheduler::promote, tk_rc.h ScConfig, k_rc_cost<PIX, true> ----
+int thor_hip_force_key_frame(thor_hip_encoder* e, int stream, int display_index) {
+  if (!e) return 1;
+  if (e->sp.num_reorder_pics != 0) return 2;   // low delay only
+  if (stream < 0 || stream >= e->S) return 1;
+  int r = 1;
+  ENC_DISPATCH(e, { r = E.eng.force_key_frame(stream, display_index, E.pending[stream] != 0); });
+  return r;
+}
+static bool sc_resolved(const thor_hip_scene_cut* sc, ScConfig& c) {
+  if (!sc) { c = ScConfig(); return true; }
+  if (sc->size != (int)sizeof(thor_hip_scene_cut)) return false;
+  return sc_resolve(sc->percent, sc->min_interval, c);
+}
+int thor_hip_scene_cut_check(const thor_hip_scene_cut* sc) {
+  ScConfig c;
+  return sc_resolved(sc, c) ? 0 : 1;
+}
+int thor_hip_set_scene_cut(thor_hip_encoder* e, int stream, const thor_hip_scene_cut* sc) {
+  ScConfig c;
+  if (!e) return 1;
+  if (e->sp.num_reorder_pics != 0) return 2;   // low delay only
+  if (stream < 0 || stream >= e->S || !sc_resolved(sc, c)) return 1;
+  if (!ENC_STREAM(e, stream, log.empty())) return 2;   // in the middle of a sequence
+  ENC_DISPATCH(e, { E.eng.set_scene_cut(stream, c); });
+  return 0;
+}
+int thor_hip_scene_cost(thor_hip_encoder* e, int stream, int slot, int prev_slot, unsigned long long sums[3]) {
+  if (!e || !sums) return 1;
+  if (e->sp.num_reorder_pics != 0) return 2;   // low delay only
+  if (stream < 0 || stream >= e->S) return 1;
+  int r = 0;
+  ENC_DISPATCH(e, {
+    auto& v = E.staged[stream];
+    auto staged = [&](int i) { return i >= 0 && i < (int)v.size() && v[i].base_y; };
+    if (!staged(slot) || (prev_slot != -1 && !staged(prev_slot))) r = 1;
+    else E.eng.scene_cost(v[slot], prev_slot == -1 ? nullptr : &v[prev_slot], sums);
+  });
+  return r;
+}
+int thor_hip_get_frame_key(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_key* out) {
+  if (!e || stream < 0 || stream >= e->S || !out) return 1;
+  const std::vector<FrameStat>& log = ENC_STREAM(e, stream, log);
+  if (i < 0 || i >= (int)log.size()) return 1;
+  memset(out, 0, sizeof(*out));
+  out->reason = log[i].key_reason;
+  out->sum_intra = log[i].key_sums[0]; out->sum_best = log[i].key_sums[1]; out->n_intra = log[i].key_sums[2];
   return 0;
 }
 void thor_hip_kernel_time(thor_hip_encoder*, double* sb_ms, long* sb_launches, double* filter_ms) {

@@ -409,11 +409,20 @@ template void launch_scale_in<uint16_t>(const void*, const PixLayout&, const Sca
 template <typename PIX> void launch_rc_cost(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n) {
   if (n <= 0) return;
   const int tiles = ((hjobs[0].hw + RC_TILE - 1) / RC_TILE) * ((hjobs[0].hh + RC_TILE - 1) / RC_TILE);
-  hipLaunchKernelGGL(k_rc_cost<PIX>, dim3(tiles, n), dim3(256), 0, g_stream, jobs);
+  hipLaunchKernelGGL((k_rc_cost<PIX, false>), dim3(tiles, n), dim3(256), 0, g_stream, jobs);
   HIPCHECK(hipGetLastError());
 }
 template void launch_rc_cost<uint8_t>(const RcJob<uint8_t>*, const RcJob<uint8_t>*, int);
 template void launch_rc_cost<uint16_t>(const RcJob<uint16_t>*, const RcJob<uint16_t>*, int);
+// The same analysis against previous ORIGINALS (RcJob::prev_y; thor_hip_scene_cost): the kernel's other instantiation, which stores nothing but the sums.
+template <typename PIX> void launch_rc_cost_orig(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n) {
+  if (n <= 0) return;
+  const int tiles = ((hjobs[0].hw + RC_TILE - 1) / RC_TILE) * ((hjobs[0].hh + RC_TILE - 1) / RC_TILE);
+  hipLaunchKernelGGL((k_rc_cost<PIX, true>), dim3(tiles, n), dim3(256), 0, g_stream, jobs);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_rc_cost_orig<uint8_t>(const RcJob<uint8_t>*, const RcJob<uint8_t>*, int);
+template void launch_rc_cost_orig<uint16_t>(const RcJob<uint16_t>*, const RcJob<uint16_t>*, int);
 
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {

@@ -845,6 +845,35 @@ extern "C" int thor_hip_kat_rc_cost(const void* cur, const void* prev_or_null, i
   else kat_rc_cost<uint16_t>((const uint16_t*)cur, (const uint16_t*)prev_or_null, w, h, out, (uint16_t*)half_out);
   return 0;
 }
+// k_rc_cost<PIX, true> on host planes: both originals in device frames with a row pitch of a multiple of 16 samples, one launch.
+template <typename PIX> static void kat_scene_cost(const PIX* cur, const PIX* prev, int w, int h, unsigned long long out[3]) {
+  const int sy = (w + 15) & ~15;
+  const size_t ny = (size_t)sy * h;
+  DevBuf<PIX> dc(ny), dp(ny);
+  DevBuf<unsigned long long> sums(4);
+  DevBuf<RcJob<PIX>> dj(1);
+  std::vector<PIX> tmp(ny, 0);
+  auto up = [&](PIX* d, const PIX* src) {
+    for (int r = 0; r < h; r++) memcpy(tmp.data() + (size_t)r * sy, src + (size_t)r * w, (size_t)w * sizeof(PIX));
+    backend::h2d(d, tmp.data(), ny * sizeof(PIX));
+  };
+  up(dc.p, cur);
+  if (prev) up(dp.p, prev);
+  RcJob<PIX> J;
+  J.y = dc.p; J.sy = sy; J.hw = w / 2; J.hh = h / 2; J.cur = nullptr; J.prev = nullptr; J.out = sums.p;
+  J.prev_y = prev ? dp.p : nullptr; J.prev_sy = sy;
+  backend::h2d(dj.p, &J, sizeof(J));
+  launch_rc_cost_orig<PIX>(dj.p, &J, 1);
+  backend::dev_sync();
+  backend::d2h(out, sums.p, 3 * sizeof(unsigned long long));
+}
+extern "C" int thor_hip_kat_scene_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3]) {
+  if (!cur || !out || w % 8 || h % 8 || w < 16 || h < 16 || w > 8192 || h > 8192 || (bitdepth != 8 && bitdepth != 10 && bitdepth != 12)) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_scene_cost<uint8_t>((const uint8_t*)cur, (const uint8_t*)prev_or_null, w, h, out);
+  else kat_scene_cost<uint16_t>((const uint16_t*)cur, (const uint16_t*)prev_or_null, w, h, out);
+  return 0;
+}
 // k_rgb_in / k_rgb_out on host buffers, like the two above: the device copy keeps the host pointer's offset from a 16-byte boundary.
 static int kat_rgb_args(const void* rgb, const void* planar, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, RgbFormat& R) {
   auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };

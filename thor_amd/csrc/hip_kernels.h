@@ -265,7 +265,10 @@ __global__ __launch_bounds__(256) void k_scale_in(const void* frame, PixLayout L
 // one lane per candidate vector for the inter cost (five rounds of 64 for the 289), DPP reductions; the lanes read neighbouring LDS addresses (the
 // candidates of a round differ in dx) and the block's sample as a broadcast.  The wavefronts' sums meet in LDS: three 64-bit atomic adds per workgroup.
 // Integer sums: the result does not depend on the order.  LDS: 3.3 KiB (8-bit) / 6.6 KiB (16-bit).
-template <typename PIX> __global__ __launch_bounds__(256) void k_rc_cost(const RcJob<PIX>* jobs) {
+// PREV_ORIG (thor_hip_scene_cost): the previous frame is a full-size original (J.prev_y), not a stored half-size plane.  Its 96 x 96 window is halved while
+// it is loaded - a lane makes four neighbouring half-size samples from two 8-sample loads (rc_half_quad) and stores them as one LDS word pair - so the
+// LDS stays what it is; the window's groups of four lie wholly inside or outside the plane (its width is a multiple of 4).  Nothing but the sums is stored.
+template <typename PIX, bool PREV_ORIG> __global__ __launch_bounds__(256) void k_rc_cost(const RcJob<PIX>* jobs) {
   const RcJob<PIX> J = jobs[blockIdx.y];
   __shared__ PIX s_cur[RC_TILE * RC_TILE];
   __shared__ PIX s_prev[RC_WIN * RC_WIN];
@@ -278,11 +281,21 @@ template <typename PIX> __global__ __launch_bounds__(256) void k_rc_cost(const R
     PIX v = 0;
     if (gx < J.hw && gy < J.hh) {
       v = (PIX)rc_half_sample(J.y, J.sy, gx, gy);
-      J.cur[(size_t)gy * J.hw + gx] = v;
+      if constexpr (!PREV_ORIG) J.cur[(size_t)gy * J.hw + gx] = v;
     }
     s_cur[i] = v;
   }
-  if (J.prev)
+  const bool has_prev = PREV_ORIG ? J.prev_y != nullptr : J.prev != nullptr;
+  if constexpr (PREV_ORIG) {
+    if (has_prev)
+      for (int i = tid; i < RC_WIN * RC_WIN / 4; i += 256) {
+        const int wx = (i % (RC_WIN / 4)) * 4, wy = i / (RC_WIN / 4);
+        const int gx = tx0 - RC_RANGE + wx, gy = ty0 - RC_RANGE + wy;
+        PIX q[4] = {0, 0, 0, 0};
+        if (gx >= 0 && gx + 4 <= J.hw && gy >= 0 && gy < J.hh) rc_half_quad(J.prev_y, J.prev_sy, gx, gy, q);
+        for (int k = 0; k < 4; k++) s_prev[wy * RC_WIN + wx + k] = q[k];
+      }
+  } else if (has_prev)
     for (int i = tid; i < RC_WIN * RC_WIN; i += 256) {
       const int gx = tx0 - RC_RANGE + i % RC_WIN, gy = ty0 - RC_RANGE + i / RC_WIN;
       s_prev[i] = gx >= 0 && gx < J.hw && gy >= 0 && gy < J.hh ? J.prev[(size_t)gy * J.hw + gx] : (PIX)0;
@@ -299,7 +312,7 @@ template <typename PIX> __global__ __launch_bounds__(256) void k_rc_cost(const R
     const int mean = (int)((sum + (unsigned)(n / 2)) / (unsigned)n);
     const unsigned intra = (unsigned)wave_sum_dpp((int)rc_block_dev(blk, RC_TILE, bw, bh, mean, lane, 64));
     unsigned inter = intra;
-    if (J.prev)
+    if (has_prev)
       inter = wave_min_u32_dpp(rc_block_inter(blk, RC_TILE, s_prev + (ly + RC_RANGE) * RC_WIN + lx + RC_RANGE, RC_WIN, bw, bh, x0, y0, J.hw, J.hh, lane, 64));
     rc_block_add(intra, inter, acc);
   }

@@ -34,6 +34,11 @@ struct CliArgs {
   // stream.  Not options of the reference: its -bitrate / -max_qp ... keep their handling below.
   int rc[7] = {0, 0, 0, 0, 0, 0, 0};  // bitrate, buffer_ms, min_qp, max_qp, min_qp_i, max_qp_i, initial_qp
   bool rc_given = false;     // one of the seven was given: front-end options like -pixfmt
+  // -key_frames a,b,c: key frames at these chunk-relative frames; -key_scenecut PCT [-key_min_interval N]: scene cuts (tk_rc.h: ScConfig).  The same for every
+  // stream, low delay only.  -key_scenecut has no default: 0 is off.
+  std::vector<int> key_frames;
+  int key_scenecut = 0, key_min_interval = 0;
+  bool key_given = false;    // one of the three was given: front-end options like -pixfmt
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -104,6 +109,23 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
         a.rc[which] = I();
         if ((a.rc[which] < 0 || (which >= 2 && a.rc[which] > 51)) && a.unsupported.empty()) a.unsupported = k + " " + v;   // the set as a whole: cli_parse
       }
+    }
+    else if (k == "-key_frames" || k == "-key_scenecut" || k == "-key_min_interval") {
+      a.key_given = true;
+      bool ok = true;
+      if (k == "-key_frames") {
+        a.key_frames.clear();
+        std::istringstream is(v);
+        std::string tok;
+        while (std::getline(is, tok, ',')) {
+          ok = ok && !tok.empty() && tok.find_first_not_of("0123456789") == std::string::npos;
+          if (ok) a.key_frames.push_back(atoi(tok.c_str()));
+        }
+        ok = ok && !a.key_frames.empty() && (int)a.key_frames.size() <= kMaxKeyRequests;
+      }
+      else if (k == "-key_scenecut") { a.key_scenecut = I(); ok = a.key_scenecut >= 0 && a.key_scenecut <= 100; }
+      else { a.key_min_interval = I(); ok = a.key_min_interval >= 0; }
+      if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
     }
     else if (k == "-width") p.width = I();
     else if (k == "-height") p.height = I();
@@ -191,6 +213,7 @@ static inline CliArgs cli_parse(int argc, char** argv) {
   if (!a.unsupported.empty()) { fprintf(stderr, "Run-time error...\noption %s is not implemented by this path (it changes the bitstream)\n...now exiting to system...\n", a.unsupported.c_str()); exit(2); }
   RcConfig rcc;
   if (a.rc_given && !rc_resolve(a.rc[0], a.rc[1], a.rc[2], a.rc[3], a.rc[4], a.rc[5], a.rc[6], rcc)) { fprintf(stderr, "Run-time error...\nthe -rc_ options do not describe a rate control (a minimum above its maximum)\n...now exiting to system...\n"); exit(2); }
+  if (a.key_given && a.sp.num_reorder_pics != 0) { fprintf(stderr, "Run-time error...\nthe -key_ options need a low-delay configuration (num_reorder_pics 0)\n...now exiting to system...\n"); exit(2); }
   return a;
 }
 
@@ -256,6 +279,15 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       // THOR_RC_SCALE=k (tests): stream s aims at (1 + k * s) times the bitrate, so that one engine holds streams with different targets
       if (const char* sc = getenv("THOR_RC_SCALE")) c.bitrate = (int)((long long)c.bitrate * (1 + atoi(sc) * s));
       eng.set_rate_control(s, c);
+    }
+  if (a.key_given)
+    for (int s = 0; s < a.streams; s++) {
+      // THOR_KEY_SHIFT=k (tests): stream s asks for its key frames k * s frames later, so that one engine holds streams with different requests
+      const int shift = getenv("THOR_KEY_SHIFT") ? atoi(getenv("THOR_KEY_SHIFT")) * s : 0;
+      for (int f : a.key_frames)
+        if (f + shift < a.num_frames && eng.force_key_frame(s, f + shift, false)) { fprintf(stderr, "Run-time error...\n-key_frames: frame %d cannot be a key frame\n...now exiting to system...\n", f + shift); return 2; }
+      ScConfig scc;
+      if (sc_resolve(a.key_scenecut, a.key_min_interval, scc) && scc.on()) eng.set_scene_cut(s, scc);
     }
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
   auto upload = [&](int s) { if (use_scale) eng.stage_scaled_host(frame.data(), eng.st[s].orig.p); else if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
@@ -338,6 +370,13 @@ template <typename PIX> int cli_run(const CliArgs& a) {
         fprintf(fl, "%d %d %d %d %d %d %d %d %llu %llu %llu %lld %d\n", s, f.display, f.frame_type, r.frame_class, r.qp_rule, r.base_qp, f.qp, f.num_bits, r.sum_intra, r.sum_best, r.n_intra,
                 r.fullness, r.overflows);
       }
+    fclose(fl);
+  }
+  if (const char* klp = getenv("THOR_KEY_LOG")) {   // tests: one line per coded frame of every stream: stream, display, type, reason, the analysis sums
+    FILE* fl = fopen(klp, "w");
+    if (!fl) { fprintf(stderr, "cannot open %s\n", klp); return 5; }
+    for (int s = 0; s < a.streams; s++)
+      for (const FrameStat& f : eng.st[s].log) fprintf(fl, "%d %d %d %d %llu %llu %llu\n", s, f.display, f.frame_type, f.key_reason, f.key_sums[0], f.key_sums[1], f.key_sums[2]);
     fclose(fl);
   }
   for (int s = 0; s < a.streams; s++) {

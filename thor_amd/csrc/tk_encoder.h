@@ -83,6 +83,8 @@ template <typename PIX> void launch_scale_in(const void* frame, const PixLayout&
                                              int height, int bitdepth, int input_bitdepth);
 // The frame analysis of rate control (tk_rc.h, k_rc_cost) of n streams, one launch on the library's stream.  jobs / hjobs: device / host arrays of n RcJob.
 template <typename PIX> void launch_rc_cost(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n);
+// The same against previous originals (RcJob::prev_y): the kernel's other instantiation, which stores nothing but the sums.
+template <typename PIX> void launch_rc_cost_orig(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -109,6 +111,7 @@ struct FrameParams {
   double lambda_coeff = 1.0;
   int b_level = 0;
   int qp_rule = 0;                         // QR_*: how qp follows from the base QP (GopScheduler::rule_qp)
+  int key_reason = 0;                      // KEY_*: why the frame is an I frame when the schedule alone would not have made it one (tk_rc.h)
 };
 enum { QR_BASE = 0, QR_I, QR_P, QR_B0, QR_B1, QR_B2, QR_B3, QR_B };
 
@@ -121,6 +124,8 @@ struct GopScheduler {
   int skip = 0, num_frames = 0, file_frames = 0;
   int frame_num0 = 0, k = 0, sub_gop = 1, num_encoded = 0, last_intra = 0, last_PorI = -1, min_interp_depth = 0;
   bool started = false;
+  int key_req[kMaxKeyRequests];   // frame numbers a key frame was asked for (thor_hip_force_key_frame), low delay only; a request leaves when its frame is scheduled
+  int n_key = 0;
   static int ilog2i(unsigned v) { int n = 0; while (v >>= 1) n++; return n; }
   static int code_to_display(int sub, int idx) {
     static const int cd1[1] = {0}, cd2[2] = {1, 0}, cd4[4] = {3, 1, 0, 2}, cd8[8] = {7, 3, 1, 5, 0, 2, 4, 6},
@@ -140,6 +145,35 @@ struct GopScheduler {
     min_interp_depth = ilog2i((unsigned)(p.num_reorder_pics + 1)) - 3;
     if (p.frame_rate > 30) min_interp_depth--;
     frame_num0 = skip; k = 0; num_encoded = 0; last_intra = 0; last_PorI = -1; started = true;
+    n_key = 0;
+  }
+  // A key frame at chunk-relative frame frame_num; false: the set is full.  A frame asked for twice is held once.
+  bool request_key(int frame_num) {
+    for (int i = 0; i < n_key; i++)
+      if (key_req[i] == frame_num) return true;
+    if (n_key == kMaxKeyRequests) return false;
+    key_req[n_key++] = frame_num;
+    return true;
+  }
+  bool take_key(int frame_num) {
+    for (int i = 0; i < n_key; i++)
+      if (key_req[i] == frame_num) { key_req[i] = key_req[--n_key]; return true; }
+    return false;
+  }
+  int intra_modes(int frame_type) const { return (sp.intra_rdo == 0 || (frame_type != F_I && sp.encoder_speed > 0)) ? 4 : 10; }
+  // Make f the I frame intra_period would have made at its place: every I frame of next() passes here, and so does a frame next() returned as a P
+  // frame that is promoted afterwards (a request for the frame already scheduled, a scene cut).  Nothing else of the schedule moves: num_encoded,
+  // the HQperiod phase and last_PorI run on; later frames drop the references older than this frame (last_intra).
+  void promote(FrameParams& f, int reason) {
+    f.frame_type = F_I;
+    f.qp_rule = QR_I;
+    f.qp = rule_qp(sp, QR_I, sp.qp);
+    f.num_ref = 0;
+    for (int r = 0; r < kMaxRefs; r++) f.ref_array[r] = 0;
+    f.num_intra_modes = intra_modes(F_I);
+    f.lambda_coeff = sp.lambda_coeffI;
+    f.key_reason = reason;
+    last_intra = f.frame_num;
   }
   // The QP of a frame from the base QP (mainenc.c:281-314): which of the dqp / mqp pairs applies is the frame's qp_rule, set by next(); the base is the
   // parameter set's qp, or the rate control's choice for the frame (Engine::rate_control).
@@ -181,6 +215,7 @@ struct GopScheduler {
       if (sp.num_reorder_pics == 0) {
         if (sp.intra_period > 0) f.frame_type = (num_encoded % sp.intra_period) == 0 ? F_I : F_P;
         else f.frame_type = num_encoded == 0 ? F_I : F_P;
+        if (n_key && take_key(f.frame_num) && f.frame_type != F_I) { f.frame_type = F_I; f.key_reason = KEY_FORCED; }
       } else {
         if (sp.intra_period > 0) f.frame_type = (f.frame_num % sp.intra_period) == 0 ? F_I : ((f.frame_num % sub_gop) == 0 ? F_P : F_B);
         else f.frame_type = f.frame_num == 0 ? F_I : ((f.frame_num % sub_gop) == 0 ? F_P : F_B);
@@ -188,7 +223,7 @@ struct GopScheduler {
       const int coded_phase = (num_encoded + sub_gop - 2) % sub_gop + 1;
       const int b_level = ilog2i((unsigned)coded_phase);
       f.b_level = b_level;
-      if (f.frame_type == F_I) { f.qp_rule = QR_I; last_intra = f.frame_num; }
+      if (f.frame_type == F_I) {}   // an I frame's fields: promote(), below; it builds no reference list
       else if (sp.num_reorder_pics == 0) f.qp_rule = (num_encoded % sp.HQperiod) ? QR_P : QR_BASE;
       else if (f.frame_num % sub_gop) f.qp_rule = !dyadic ? QR_B : b_level == 0 ? QR_B0 : b_level == 1 ? QR_B1 : b_level == 2 ? QR_B2 : b_level == 3 ? QR_B3 : QR_B;
       else f.qp_rule = (f.frame_num % sp.HQperiod) ? QR_P : QR_BASE;
@@ -250,8 +285,8 @@ struct GopScheduler {
             f.num_ref--;
           }
       for (int r = 0; r < kMaxRefs; r++) f.ref_array[r] = ra[r];
-      f.num_intra_modes = (sp.intra_rdo == 0 || (f.frame_type != F_I && sp.encoder_speed > 0)) ? 4 : 10;
-      if (f.frame_type == F_I) f.lambda_coeff = sp.lambda_coeffI;
+      f.num_intra_modes = intra_modes(f.frame_type);
+      if (f.frame_type == F_I) promote(f, f.key_reason);
       else if (f.frame_type == F_P) f.lambda_coeff = sp.lambda_coeffP;
       else f.lambda_coeff = b_level == 0 ? sp.lambda_coeffB0 : b_level == 1 ? sp.lambda_coeffB1 : b_level == 2 ? sp.lambda_coeffB2
                                                                               : b_level == 3 ? sp.lambda_coeffB3 : sp.lambda_coeffB;
@@ -395,6 +430,10 @@ template <typename PIX> struct Stream {
   bool rc_prev = false;                  // the other plane holds the previous frame of this sequence
   RcStat rc_cur;                         // the frame in flight: the decision and its analysis sums
   std::vector<RcStat> rclog;             // one record per coded frame, like `log`
+  // scene cuts (tk_rc.h: ScConfig; off unless Engine::set_scene_cut turned them on).  They share the analysis and its two half planes with rate control.
+  ScConfig sc;
+  bool key_analysed = false;             // the frame in flight was analysed: key_sums goes into its record
+  unsigned long long key_sums[3] = {0, 0, 0};
 };
 
 // The caller-visible fields of the reference's deblock_data_t (common/types.h:178-187) in declaration order, from one DbCell:
@@ -447,6 +486,8 @@ template <typename PIX> class Engine {
   bool scale_dirty = true;
   RcJob<PIX>* d_rcjobs = nullptr;         // rate control: the analysis jobs and, per stream, four slots for the three sums (allocated on first use)
   unsigned long long* d_rcsums = nullptr;
+  RcJob<PIX>* d_scjob = nullptr;          // scene_cost: its one job and its sums (allocated on first use)
+  unsigned long long* d_scsums = nullptr;
 
   // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
   int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
@@ -564,6 +605,8 @@ template <typename PIX> class Engine {
     backend::dev_free(d_scale); d_scale = nullptr; scale_dirty = true;
     backend::dev_free(d_rcjobs); d_rcjobs = nullptr;
     backend::dev_free(d_rcsums); d_rcsums = nullptr;
+    backend::dev_free(d_scjob); d_scjob = nullptr;
+    backend::dev_free(d_scsums); d_scsums = nullptr;
   }
 
   // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
@@ -777,6 +820,48 @@ template <typename PIX> class Engine {
   void begin_sequence(int s, int skip, int num_frames, int file_frames) {
     st[s].gop.init(sp, skip, num_frames, file_frames); st[s].log.clear();
     if (st[s].rc.on()) set_rate_control(s, st[s].rc);   // the target stays, the controller starts again
+    if (st[s].sc.on()) st[s].rc_prev = false;           // the scene-cut setting stays too; the next analysis has no previous frame
+  }
+  bool low_delay() const { return sp.num_reorder_pics == 0; }
+  // Scene cuts of stream s from its next frame on (c.on() false: off); legal where set_rate_control is - the caller checks, and that the stream is low delay.
+  void set_scene_cut(int s, const ScConfig& c) {
+    st[s].sc = c;
+    st[s].rc_prev = false;
+  }
+  // A key frame at chunk-relative frame idx of the low-delay stream s.  pending: st[s].cur is scheduled and not coded yet.  0; 1: idx is outside the
+  // chunk or coded already, or the set is full.
+  int force_key_frame(int s, int idx, bool pending) {
+    Stream<PIX>& q = st[s];
+    if (!q.gop.started) q.gop.init(sp, 0, 1 << 28, 1 << 28);
+    if (idx < 0 || idx >= q.gop.num_frames) return 1;
+    if (pending && q.cur.frame_num == idx) {
+      if (q.cur.frame_type != F_I) q.gop.promote(q.cur, KEY_FORCED);
+      return 0;
+    }
+    if (idx < q.gop.num_encoded + (pending ? 1 : 0)) return 1;   // low delay: the coded index is the frame number
+    return q.gop.request_key(idx) ? 0 : 1;
+  }
+  // The analysis (tk_rc.h) of the original `cur` against the original `prev` (nullptr: none, inter = intra) as a call of its own: k_rc_cost's second
+  // instantiation halves the previous original itself, so neither a stream's half planes nor its controller are touched.
+  void scene_cost(const DevFrame<PIX>& cur, const DevFrame<PIX>* prev, unsigned long long sums[3]) {
+    if (!d_scsums) {
+      d_scsums = (unsigned long long*)backend::dev_alloc(4 * sizeof(unsigned long long));
+      d_scjob = (RcJob<PIX>*)backend::dev_alloc(sizeof(RcJob<PIX>));
+    }
+    RcJob<PIX> J;
+    J.y = cur.p.y; J.sy = cur.p.sy; J.hw = sp.width / 2; J.hh = sp.height / 2;
+    J.cur = nullptr; J.prev = nullptr;
+    J.prev_y = prev ? prev->p.y : nullptr; J.prev_sy = prev ? prev->p.sy : 0;
+    J.out = d_scsums;
+    backend::dev_memset(d_scsums, 0, 4 * sizeof(unsigned long long));
+#if TK_HOST
+    rc_cost_frame(J, true);
+#else
+    backend::h2d(d_scjob, &J, sizeof(J));
+    launch_rc_cost_orig<PIX>(d_scjob, &J, 1);
+#endif
+    backend::dev_sync();
+    backend::d2h(sums, d_scsums, 3 * sizeof(unsigned long long));
   }
   // Rate control of stream s from its next frame on (tk_rc.h; c.on() false: off).  Legal while the stream's log is empty: before its first frame or right
   // after begin_sequence - the caller checks.  The controller starts empty and the next analysis has no previous frame.
@@ -790,6 +875,8 @@ template <typename PIX> class Engine {
   }
   // The base QP of the frames fp[s] of the rate-controlled streams in [first, first + count), origs in place: one analysis launch for all of them, the
   // three sums of each back to the host, the controller's decision, and the frame's QP from it by the rule the schedule gave the frame.
+  // A stream with scene cuts on is analysed too, rate-controlled or not; per stream the order is analysis, cut decision and promotion (a P frame
+  // becomes the I frame GopScheduler::promote makes), and only then the controller, which therefore sees a promoted frame as class 0.
   void rate_control(std::vector<FrameParams>& fp, int first, int count) {
     std::vector<RcJob<PIX>> hj;
     std::vector<int> who;
@@ -800,7 +887,7 @@ template <typename PIX> class Engine {
     }
     for (int s = first; s < first + count; s++) {
       Stream<PIX>& q = st[s];
-      if (!q.rc.on()) continue;
+      if (!q.rc.on() && !q.sc.on()) continue;
       for (int k = 0; k < 2; k++)
         if (!q.rc_half[k]) q.rc_half[k] = (PIX*)backend::dev_alloc((size_t)hw * hh * sizeof(PIX));
       RcJob<PIX> J;
@@ -825,8 +912,16 @@ template <typename PIX> class Engine {
       const int s = who[k];
       Stream<PIX>& q = st[s];
       FrameParams& f = fp[s];
+      const bool had_prev = q.rc_prev;
       q.rc_flip ^= 1;
       q.rc_prev = true;
+      q.key_analysed = true;
+      for (int j = 0; j < 3; j++) q.key_sums[j] = sums[(size_t)(s - first) * 4 + j];
+      if (f.frame_type == F_P && q.gop.started && low_delay() && sc_is_cut(q.sc, had_prev, f.frame_num, q.gop.last_intra, q.key_sums[0], q.key_sums[1])) {
+        q.gop.promote(f, KEY_SCENE_CUT);
+        q.cur = f;
+      }
+      if (!q.rc.on()) continue;
       RcStat& r = q.rc_cur;
       r = RcStat();
       r.frame_class = rc_class(f.frame_type, f.b_level);
@@ -953,7 +1048,7 @@ template <typename PIX> class Engine {
   // With rate control on for one of them the frames' QPs are chosen here (rate_control), which is why fp is not const.
   void prepare_jobs(std::vector<FrameParams>& fp, int first, int count) {
     for (int s = first; s < first + count; s++)
-      if (st[s].rc.on()) { rate_control(fp, first, count); break; }
+      if (st[s].rc.on() || st[s].sc.on()) { rate_control(fp, first, count); break; }
     if (!external_interp) make_interp_frames(fp, first, count);
     for (int s = first; s < first + count; s++) {
       Stream<PIX>& q = st[s];
@@ -1056,6 +1151,11 @@ template <typename PIX> class Engine {
         r.ref_frame_num[k] = f.ref_array[k] >= 0 && f.ref_array[k] < ring_size ? q.ring[f.ref_array[k]].frame_num : -1;
       }
       r.num_bits = -q.bits.nbits;  // completed below, when the frame's bits are assembled
+      r.key_reason = f.key_reason;
+      if (q.key_analysed) {
+        for (int k = 0; k < 3; k++) r.key_sums[k] = q.key_sums[k];
+        q.key_analysed = false;
+      }
       q.log.push_back(r);
     }
     // sliding window: the slot shifted out becomes ref[0] (encode_frame.c:826-835)

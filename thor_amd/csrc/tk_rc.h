@@ -8,6 +8,9 @@
 // wavefront of the superblock kernel cannot follow): every frame is coded at ONE QP and stays exactly what the block path produces at that QP.
 #pragma once
 #include "tk_common.h"
+#if TK_HOST
+#include <vector>
+#endif
 
 namespace tk {
 
@@ -26,12 +29,26 @@ template <typename PIX> struct RcJob {
   PIX* cur;                 // half-size plane written by this analysis, hw samples per row
   const PIX* prev;          // the plane the previous analysis of the stream wrote; nullptr: none (inter cost = intra cost)
   unsigned long long* out;  // sum_intra, sum_best, n_intra: added to (cleared by the caller)
+  // the variant that takes the previous frame as a full-size ORIGINAL (k_rc_cost<PIX, true>, thor_hip_scene_cost): halved while it is loaded; `cur` and `prev`
+  // are not used then, and nothing is stored but the sums
+  const PIX* prev_y = nullptr;   // luma of the previous original, 16-byte aligned like y; nullptr: none
+  int prev_sy = 0;               // a multiple of 8 samples
 };
 
 // sample (x, r) of the half-size plane: (a + b + c + d + 2) >> 2 over the 2x2 quad
 template <typename PIX> TK_DEV int rc_half_sample(const PIX* y, int sy, int x, int r) {
   const PIX* p = y + (size_t)(2 * r) * sy + 2 * x;
   return ((int)p[0] + (int)p[1] + (int)p[sy] + (int)p[sy + 1] + 2) >> 2;
+}
+// Four neighbouring samples (x .. x + 3, r) of the half-size plane at once, x a multiple of 4: two loads of 8 full-size samples (8 or 16 bytes each; the
+// rows of a staged frame start 16-byte aligned and 2 * x is a multiple of 8), the same rounding as rc_half_sample.
+template <typename PIX> TK_DEV void rc_half_quad(const PIX* y, int sy, int x, int r, PIX out[4]) {
+  struct alignas(8 * sizeof(PIX)) Row { PIX v[8]; };
+  const PIX* p = y + (size_t)(2 * r) * sy + 2 * x;
+  Row a, b;
+  __builtin_memcpy(&a, __builtin_assume_aligned(p, sizeof(Row)), sizeof(Row));
+  __builtin_memcpy(&b, __builtin_assume_aligned(p + sy, sizeof(Row)), sizeof(Row));
+  for (int k = 0; k < 4; k++) out[k] = (PIX)(((int)a.v[2 * k] + (int)a.v[2 * k + 1] + (int)b.v[2 * k] + (int)b.v[2 * k + 1] + 2) >> 2);
 }
 // The three block functions take a bw x bh block (bw, bh: 4 or 8) at b, bs samples per row, and return this lane's share: the caller adds the
 // lanes' sums (rc_block_sum, rc_block_dev) or takes their minimum (rc_block_inter).  32-bit: 64 samples of 4095 do not fit 16 bits.
@@ -73,7 +90,20 @@ TK_DEV void rc_block_add(unsigned intra, unsigned inter, unsigned long long acc[
 
 #if TK_HOST
 // The analysis of one frame with one lane: what k_rc_cost computes tile by tile.
-template <typename PIX> static inline void rc_cost_frame(const RcJob<PIX>& J) {
+// prev_orig (k_rc_cost<PIX, true>): the previous frame is J.prev_y, halved here four samples at a time as the kernel does; no plane is stored.
+template <typename PIX> static inline void rc_cost_frame(const RcJob<PIX>& J0, bool prev_orig = false) {
+  RcJob<PIX> J = J0;
+  std::vector<PIX> hcur, hprev;
+  if (prev_orig) {
+    hcur.resize((size_t)J.hw * J.hh);
+    J.cur = hcur.data(); J.prev = nullptr;
+    if (J.prev_y) {
+      hprev.resize((size_t)J.hw * J.hh);
+      for (int r = 0; r < J.hh; r++)
+        for (int x = 0; x < J.hw; x += 4) rc_half_quad(J.prev_y, J.prev_sy, x, r, hprev.data() + (size_t)r * J.hw + x);
+      J.prev = hprev.data();
+    }
+  }
   for (int r = 0; r < J.hh; r++)
     for (int x = 0; x < J.hw; x++) J.cur[(size_t)r * J.hw + x] = (PIX)rc_half_sample(J.y, J.sy, x, r);
   unsigned long long acc[3] = {0, 0, 0};
@@ -199,5 +229,25 @@ struct RcStat {  // one coded frame of a rate-controlled stream (thor_hip_frame_
   long long fullness = 0, buffer_bits = 0, target_bits = 0;
   int overflows = 0;
 };
+
+// ---- key frames (include/thor_hip.h: thor_hip_scene_cut states the rule) -----------------------------------------------------------------------
+constexpr int kMaxKeyRequests = 64;   // pending thor_hip_force_key_frame requests per stream
+enum { KEY_SCHEDULE = 0, KEY_FORCED = 1, KEY_SCENE_CUT = 2 };
+struct ScConfig {  // thor_hip_scene_cut, resolved
+  int percent = 0, min_interval = 0;
+  bool on() const { return percent > 0; }
+};
+static inline bool sc_resolve(int percent, int min_interval, ScConfig& c) {
+  if (percent < 0 || percent > 100 || min_interval < 0) return false;
+  c.percent = percent; c.min_interval = min_interval;
+  return true;
+}
+// Is the P frame frame_num of a stream whose last I frame was last_intra a scene cut?  had_prev: its analysis had a previous plane.  The sums are at most
+// 2^36 (kRcCostMax: an 8192 x 8192 frame of 12-bit samples) and percent at most 100 < 2^7, so both products stay below 2^43.
+static inline bool sc_is_cut(const ScConfig& c, bool had_prev, int frame_num, int last_intra, unsigned long long sum_intra, unsigned long long sum_best) {
+  if (!c.on() || !had_prev) return false;
+  if (frame_num - last_intra < (c.min_interval > 1 ? c.min_interval : 1)) return false;
+  return sum_intra > 0 && sum_best * 100ull >= (unsigned long long)c.percent * sum_intra;
+}
 
 }  // namespace tk

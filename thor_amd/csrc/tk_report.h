@@ -21,6 +21,8 @@ struct FrameStat {
   int ref_frame_num[6] = {0, 0, 0, 0, 0, 0};  // chunk-relative frame_num of the window frame ref_array[i] points at
   int has_sse = 0;                 // sse measured (frame distortion on)
   unsigned long long sse[3] = {0, 0, 0};       // Y, U, V: sum over the plane of (original - final reconstruction)^2
+  int key_reason = 0;              // KEY_* (tk_rc.h): 0 the schedule's own type, 1 a forced key frame, 2 a scene cut
+  unsigned long long key_sums[3] = {0, 0, 0};  // sum_intra, sum_best, n_intra of the frame's analysis; zero when it was not analysed
 };
 
 // snr_yuv (common/snr.c:56-62): plse = sse / (maxsignal * maxsignal * ydim * xdim) in double, in that order; the Y loop's float cast

@@ -5,6 +5,7 @@
  *               [-rgbmatrix 601|709|2020] [-rgbrange limited|full] [-rgbsite centre|left]
  *               [-src_width W -src_height H] [-scale_filter bilinear|bicubic] [-scale_site left|centre]
  *               [-rc_bitrate N] [-rc_buffer_ms M] [-rc_min_qp Q -rc_max_qp Q] [-rc_min_qpI Q -rc_max_qpI Q] [-rc_initial_qp Q]
+ *               [-key_frames a,b,c] [-key_scenecut PCT] [-key_min_interval N]
  * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
  * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
  * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
@@ -15,6 +16,8 @@
  * the device while they are staged (thor_hip_stage_frame_scaled; defaults bicubic, left); -rf stays at the coded size.
  * -rc_bitrate N: the library's rate control (thor_hip_set_rate_control) at N bits per second, the same target for every stream; the other -rc_ options are
  * the fields of thor_hip_rate_control.  They are not the reference's -bitrate / -max_qp ..., which stay refused.
+ * -key_frames a,b,c: key frames at these frames of every stream's chunk (thor_hip_force_key_frame); -key_scenecut PCT [-key_min_interval N]: scene cuts
+ * (thor_hip_set_scene_cut; no default, 0 is off).  Low-delay configurations only.
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -59,6 +62,9 @@ int main(int argc, char** argv) {
   const char *scalefilter = "bicubic", *scalesite = "left";
   int src_w = 0, src_h = 0, scaled = 0;
   thor_hip_rate_control rc = {sizeof(thor_hip_rate_control), 0, 0, 0, 0, 0, 0, 0};
+  thor_hip_scene_cut sc = {sizeof(thor_hip_scene_cut), 0, 0};
+  const char* key_frames = NULL;
+  int key_given = 0;
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -90,6 +96,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-rc_min_qpI")) rc.min_qp_i = atoi(v);
     else if (!strcmp(k, "-rc_max_qpI")) rc.max_qp_i = atoi(v);
     else if (!strcmp(k, "-rc_initial_qp")) rc.initial_qp = atoi(v);
+    else if (!strcmp(k, "-key_frames")) { key_frames = v; key_given = 1; }
+    else if (!strcmp(k, "-key_scenecut")) { sc.percent = atoi(v); key_given = 1; }
+    else if (!strcmp(k, "-key_min_interval")) { sc.min_interval = atoi(v); key_given = 1; }
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -122,6 +131,8 @@ int main(int argc, char** argv) {
   if (scaled && (scale.filter < 0 || scale.chroma_site < 0)) { fprintf(stderr, "Run-time error...\noption -scale_filter %s -scale_site %s is unknown\n...now exiting to system...\n", scalefilter, scalesite); return 2; }
   if (scaled && (rgb || !thor_hip_scale_bytes_for(p.width, p.height, p.input_bitdepth, &scale, lay))) { fprintf(stderr, "Run-time error...\n-src_width %d -src_height %d with -pixfmt %s cannot be resampled to %dx%d\n...now exiting to system...\n", scale.src_width, scale.src_height, pixfmt, p.width, p.height); return 2; }
   if (thor_hip_rate_control_check(&rc)) { fprintf(stderr, "Run-time error...\nthe -rc_ options do not describe a rate control (a negative value, a minimum above its maximum, a QP above 51)\n...now exiting to system...\n"); return 2; }
+  if (key_given && p.num_reorder_pics != 0) { fprintf(stderr, "Run-time error...\nthe -key_ options need a low-delay configuration (num_reorder_pics 0)\n...now exiting to system...\n"); return 2; }
+  if (thor_hip_scene_cut_check(&sc) || (key_frames && key_frames[strspn(key_frames, "0123456789,")])) { fprintf(stderr, "Run-time error...\nthe -key_ options do not describe key frames (-key_scenecut 0 .. 100, -key_min_interval >= 0, -key_frames a,b,c)\n...now exiting to system...\n"); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
   size_t fsz = rgb ? thor_hip_rgb_bytes(e, rgb) : thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth, or RGB frames */
@@ -149,6 +160,15 @@ int main(int argc, char** argv) {
     if (thor_hip_begin_sequence(e, s, skip + s * n, n, (int)file_frames)) { fprintf(stderr, "bad sequence bounds\n"); return 5; }
   for (int s = 0; s < S && rc.bitrate; s++)
     if (thor_hip_set_rate_control(e, s, &rc)) { fprintf(stderr, "rate control refused\n"); return 5; }
+  for (int s = 0; s < S && key_given; s++) {
+    /* THOR_KEY_SHIFT=k (tests): stream s asks for its key frames k * s frames later */
+    int shift = getenv("THOR_KEY_SHIFT") ? atoi(getenv("THOR_KEY_SHIFT")) * s : 0;
+    for (const char* q = key_frames; q && *q; q += strcspn(q, ","), q += *q == ',') {
+      int f = atoi(q) + shift;
+      if (f < n && thor_hip_force_key_frame(e, s, f)) { fprintf(stderr, "Run-time error...\n-key_frames: frame %d cannot be a key frame\n...now exiting to system...\n", f); return 2; }
+    }
+    if (sc.percent && thor_hip_set_scene_cut(e, s, &sc)) { fprintf(stderr, "scene cut refused\n"); return 5; }
+  }
   unsigned char** recs = (unsigned char**)calloc((size_t)S * n, sizeof(unsigned char*));
   double t0 = now_s(), tenc = 0;
   int coded = 0;
@@ -198,6 +218,18 @@ int main(int argc, char** argv) {
         fclose(sf);
       }
     }
+  }
+  if (getenv("THOR_KEY_LOG")) { /* tests: one line per coded frame of every stream: stream, display, type, reason, the analysis sums */
+    FILE* fl = fopen(getenv("THOR_KEY_LOG"), "w");
+    if (!fl) { fprintf(stderr, "cannot open %s\n", getenv("THOR_KEY_LOG")); return 5; }
+    for (int s = 0; s < S; s++)
+      for (int f = 0; f < thor_hip_frame_stats_count(e, s); f++) {
+        thor_hip_frame_stats fs;
+        thor_hip_frame_key fk;
+        if (thor_hip_get_frame_stats(e, s, f, &fs) || thor_hip_get_frame_key(e, s, f, &fk)) return 5;
+        fprintf(fl, "%d %d %d %d %llu %llu %llu\n", s, fs.display_index, fs.frame_type, fk.reason, fk.sum_intra, fk.sum_best, fk.n_intra);
+      }
+    fclose(fl);
   }
   n = coded;
   double sb_ms = 0, filt_ms = 0; long launches = 0;
