@@ -387,6 +387,52 @@ typedef struct thor_hip_frame_key {
 /* Record i (coding order, the index of thor_hip_get_frame_stats) of a stream.  Returns 0; 1 on a bad argument. */
 int thor_hip_get_frame_key(const thor_hip_encoder* e, int stream, int i, thor_hip_frame_key* out);
 
+/* Temporal noise filter: the staged original of one frame filtered against up to four other staged originals of the same stream - past and / or future frames -
+ * with block motion compensation, into another staging slot at the engine's depth.  The filter is NOT recursive: its inputs are originals only and its output is
+ * a pure function of them.  A filtered frame is an ordinary staged frame: the encoder codes it like any other, and every frame's distortion (sse, psnr, the
+ * report) is measured against the slot that was coded - the FILTERED frame, not the source.  Integers only; everything below is normative, and
+ * tests/tf_model.py restates it.  s = strength (1 .. 16), sh = bitdepth - 8; samples are at the engine's depth (after the widening of a lower input depth).
+ *
+ * Luma search.  The luma plane is cut into 8x8 blocks (width and height are multiples of 8).  For each neighbour k the block's vector is the candidate (dx, dy)
+ * of [-8, 8]^2, full-pel, with the least (SAD, rank): SAD = sum |cur(x, y) - nb_k(x + dx, y + dy)| over the block; rank = 0 for the zero vector, otherwise
+ * 1 + (dy + 8) * 17 + (dx + 8).  A candidate whose displaced block leaves the plane is skipped (no padding; the zero vector never is).  Flat content therefore
+ * keeps the zero vector, and the order of the candidates is total.
+ * Block weight.  m = SAD >> sh, Tb = 128 * s, wb = B[dist] * max(0, Tb - m) / Tb (integer division), B[1] = 192, B[2] = 128 (Q8), dist = ref_dist[k].
+ * A neighbour that does not show the scene (beyond a scene cut, say) matches no block within Tb - an average difference of 2 s per sample - so every wb is 0
+ * and the frame comes out unchanged.
+ * Sample weight.  For the current sample c and the motion-compensated neighbour sample r = nb_k(x + dx, y + dy): d = |c - r| >> sh, Ts = 4 * s,
+ * ws = max(0, Ts - d), w = wb * ws.
+ * Output sample.  (c * W0 + sum_k r_k * w_k + D / 2) / D with W0 = 256 * Ts and D = W0 + sum_k w_k (integer division of non-negative values).  D <= 2^16 and
+ * the numerator stays below 2^29: 32 bits suffice.  Identical neighbours give back c exactly; nrefs = 0 copies the frame.
+ * Chroma.  Each 8x8 luma block owns one 4x4 block per chroma plane; its vector is (dx >> 1, dy >> 1) with arithmetic shifts, full-pel - that block lies inside
+ * the chroma plane whenever the luma block lies inside the luma plane; it takes the same wb, and ws comes from the chroma difference.
+ * Sub-pel vectors, a hierarchical search and overlapped blocks are deliberately left out.
+ * Device: k_tf_search (one workgroup per 32x32 luma tile and neighbour, the tile and the neighbour's 48x48 window in LDS, one lane per candidate) and
+ * k_tf_blend (one lane per four samples): two launches for all requests of a call, one synchronisation. */
+typedef struct thor_hip_temporal_filter {
+  int size;       /* sizeof(thor_hip_temporal_filter) */
+  int strength;   /* 1 .. 16 */
+} thor_hip_temporal_filter;
+typedef struct thor_hip_tf_request {
+  int stream;
+  int dst_slot;      /* receives the filtered frame; allocated on demand like any slot */
+  int slot;          /* the frame to filter */
+  int nrefs;         /* 0 .. 4 */
+  int ref_slot[4];   /* the neighbours, staged originals of the same stream */
+  int ref_dist[4];   /* their temporal distance from `slot`, 1 or 2, in either direction */
+} thor_hip_tf_request;
+/* 0 when thor_hip_filter_staged would accept *tf; 1 otherwise: NULL, a wrong `size`, a strength outside 1 .. 16.  Needs no encoder and no device. */
+int thor_hip_temporal_filter_check(const thor_hip_temporal_filter* tf);
+/* Filter `n` requests in one call - different streams, or several frames of one stream; a request's neighbour may be another request's source.  Synchronous at
+ * return.  Returns 0; 1 for a bad argument (n outside 1 .. 4096, a stream, nrefs or ref_dist out of range), a refused *tf, a source or neighbour slot that is
+ * not staged, a dst_slot that is a source or a neighbour of any request of the call, or two requests of one stream with the same destination - all found before
+ * the device is touched, and nothing is written or allocated then.  While nobody calls it the encoder launches, copies, allocates and synchronises exactly as
+ * before. */
+int thor_hip_filter_staged(thor_hip_encoder* e, const thor_hip_tf_request* req, int n, const thor_hip_temporal_filter* tf);
+/* The staged frame in `slot`, as it would be coded: packed planar 4:2:0 at the ENGINE's depth (bytes for bitdepth 8, little-endian uint16 otherwise: width *
+ * height * 3 / 2 samples).  Returns 0; 1 for a bad argument or a slot that is not staged. */
+int thor_hip_get_staged(thor_hip_encoder* e, int stream, int slot, void* yuv_out);
+
 /* HIP-event time (ms) and launch count of the superblock kernel accumulated since the last
  * reset; used by bench.py for the roofline figure. */
 void thor_hip_kernel_time(thor_hip_encoder* e, double* sb_ms, long* sb_launches, double* filter_ms);
@@ -618,6 +664,12 @@ int thor_hip_kat_rc_cost(const void* cur, const void* prev_or_null, int w, int h
 /* The kernel's other instantiation, the one behind thor_hip_scene_cost: one launch on `cur` with `prev_or_null` as a full-size original that the kernel halves
  * while it loads it.  The planes are copied into device frames whose rows start 16-byte aligned, as staged frames do.  Same arguments and return values. */
 int thor_hip_kat_scene_cost(const void* cur, const void* prev_or_null, int w, int h, int bitdepth, unsigned long long out[3]);
+/* k_tf_search and k_tf_blend, the temporal filter, as the engine launches them for one request.  cur: a packed planar 4:2:0 frame of w x h samples at `bitdepth`
+ * (bytes for 8, uint16_t for 10 / 12); refs: nrefs (0 .. 4) such frames one after the other; dists: 1 or 2 each.  The frames are copied into device frames laid
+ * out like staging slots.  out: the filtered frame; mv: per neighbour and 8x8 block (raster order) dx, dy; wb: per neighbour and block the block weight - so
+ * that a mismatch names its stage.  w, h: multiples of 8, at least 16.  Returns 0, 1 = bad argument, 3 = no device. */
+int thor_hip_kat_temporal_filter(const void* cur, const void* refs, const int* dists, int nrefs, int w, int h, int bitdepth, int strength, void* out, int* mv,
+                                 int* wb);
 /* The same for k_rgb_in / k_rgb_out: `src` / `dst` hold thor_hip_rgb_bytes_for(w, h, fmt) bytes in `fmt` (dst: plus 64 guard bytes, all of it uploaded
  * before the kernel runs and downloaded afterwards); the planar frames are at `bitdepth` (k_rgb_out rounds back to input_bitdepth first).  Any depth
  * of `fmt` goes with any input_bitdepth <= bitdepth.  Same return values. */

@@ -186,6 +186,23 @@ class FrameKey(C.Structure):
     _fields_ = [('reason', C.c_int), ('sum_intra', C.c_ulonglong), ('sum_best', C.c_ulonglong), ('n_intra', C.c_ulonglong)]
 
 
+class TemporalFilter(C.Structure):
+    """thor_hip_temporal_filter (include/thor_hip.h): the strength, 1 .. 16, of the motion-compensated temporal noise filter of staged frames."""
+    _fields_ = [('size', C.c_int), ('strength', C.c_int)]
+
+    def __init__(self, strength=6):
+        super().__init__(C.sizeof(TemporalFilter), strength)
+
+    def ok(self):
+        """thor_hip_temporal_filter_check: would thor_hip_filter_staged accept it?  Needs no device."""
+        return lib().thor_hip_temporal_filter_check(C.byref(self)) == 0
+
+
+class TfRequest(C.Structure):
+    """thor_hip_tf_request (include/thor_hip.h): filter the staged frame `slot` of `stream` against the staged frames ref_slot (ref_dist 1 or 2 each) into dst_slot."""
+    _fields_ = [('stream', C.c_int), ('dst_slot', C.c_int), ('slot', C.c_int), ('nrefs', C.c_int), ('ref_slot', C.c_int * 4), ('ref_dist', C.c_int * 4)]
+
+
 def lib():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _LIB
@@ -262,6 +279,10 @@ def lib():
         L.thor_hip_set_scene_cut.argtypes = [C.c_void_p, C.c_int, C.POINTER(SceneCut)]
         L.thor_hip_scene_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
         L.thor_hip_get_frame_key.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrameKey)]
+        L.thor_hip_temporal_filter_check.argtypes = [C.POINTER(TemporalFilter)]
+        L.thor_hip_filter_staged.argtypes = [C.c_void_p, C.POINTER(TfRequest), C.c_int, C.POINTER(TemporalFilter)]
+        L.thor_hip_get_staged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.thor_hip_kat_temporal_filter.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.thor_hip_params_from_config.argtypes = [C.POINTER(ThorParams), C.c_char_p]
         L.thor_hip_params_set.argtypes = [C.POINTER(ThorParams), C.c_char_p, C.c_char_p]
         L.thor_hip_params_set_sb_size.argtypes = [C.POINTER(ThorParams), C.c_int]
@@ -573,6 +594,24 @@ class Encoder:
         if r:
             raise ValueError('scene cost refused: ' + ('the parameter set is not low delay' if r == 2 else 'bad stream or a slot that is not staged'))
         return [int(v) for v in sums]
+
+    def filter_staged(self, requests, tf):
+        """thor_hip_filter_staged: `requests` is a list of (stream, dst_slot, slot, [(ref_slot, ref_dist), ...]) with up to four neighbours each, all filtered in
+        one call with the TemporalFilter `tf`.  Raises ValueError when the library refuses the call (nothing is written then)."""
+        arr = (TfRequest * max(1, len(requests)))()
+        for r, (stream, dst_slot, slot, refs) in zip(arr, requests):
+            r.stream, r.dst_slot, r.slot, r.nrefs = stream, dst_slot, slot, len(refs)
+            for k, (ref_slot, ref_dist) in enumerate(refs[:4]):
+                r.ref_slot[k], r.ref_dist[k] = ref_slot, ref_dist
+        if lib().thor_hip_filter_staged(self.h, arr, len(requests), C.byref(tf) if tf is not None else None):
+            raise ValueError('temporal filter refused: a bad request or strength, a slot that is not staged, or a destination that is a source or is given twice')
+
+    def staged(self, stream, slot):
+        """The staged frame in `slot` as it would be coded (thor_hip_get_staged): a flat packed planar 4:2:0 array at the engine's depth."""
+        out = np.zeros(self.p.width * self.p.height * 3 // 2, dtype=_pix(self.p.bitdepth))
+        if lib().thor_hip_get_staged(self.h, stream, slot, _vp(out)):
+            raise ValueError('bad stream or a slot that is not staged')
+        return out
 
     def report(self, stream):
         """The reference encoder's stdout report for the stream so far (thor_hip_report)."""
@@ -1036,3 +1075,20 @@ def kat_scene_cost(cur, prev, bitdepth):
     sums = (C.c_ulonglong * 3)()
     _kat('thor_hip_kat_scene_cost', _vp(cur), _vp(prev) if prev is not None else None, w, h, bitdepth, sums)
     return [int(v) for v in sums]
+
+
+def kat_temporal_filter(cur, refs, dists, depth, strength):
+    """thor_hip_kat_temporal_filter: k_tf_search and k_tf_blend on the frame `cur` = (Y, U, V) against the frames `refs` (up to four such triples, dists 1 or 2
+    each), as the engine launches them for one request.  Returns ((Y, U, V) filtered, mv int32 (nrefs, h / 8, w / 8, 2) as (dx, dy), wb int32 (nrefs, h / 8, w / 8))."""
+    T = _pix(depth)
+    h, w = cur[0].shape
+    pack = lambda f: np.concatenate([np.ascontiguousarray(p, dtype=T).ravel() for p in f])
+    c = pack(cur)
+    r = np.concatenate([pack(f) for f in refs]) if len(refs) else np.zeros(1, dtype=T)
+    d = (C.c_int * 4)(*list(dists))
+    out = np.zeros(w * h * 3 // 2, dtype=T)
+    mv = np.zeros((len(refs), h // 8, w // 8, 2), dtype=np.int32)
+    wb = np.zeros((len(refs), h // 8, w // 8), dtype=np.int32)
+    _kat('thor_hip_kat_temporal_filter', _vp(c), _vp(r), d, len(refs), w, h, depth, strength, _vp(out), _vp(mv), _vp(wb))
+    ny, nc = w * h, (w // 2) * (h // 2)
+    return (out[:ny].reshape(h, w), out[ny:ny + nc].reshape(h // 2, w // 2), out[ny + nc:].reshape(h // 2, w // 2)), mv, wb

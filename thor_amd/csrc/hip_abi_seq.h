@@ -114,7 +114,7 @@ int thor_hip_params_set(thor_hip_params* p, const char* name, const char* value)
   from_seq(p, a.sp);
   if (!a.unknown.empty()) return 1;      // not an option of the reference's table
   if (!a.unsupported.empty()) return 2;  // known, but this value is not implemented (qmtx, rate control, 4:4:4 ...)
-  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given || a.rc_given || a.key_given) return 3;  // front-end option, not an encoder parameter
+  if (!a.infile.empty() || !a.outfile.empty() || !a.recfile.empty() || a.num_frames != 600 || a.skip != 0 || a.streams != 1 || a.pixfmt != "i420" || a.rgb_given || a.scale_given || a.rc_given || a.key_given || a.tf_given) return 3;  // front-end option, not an encoder parameter
   return 0;
 }
 
@@ -529,6 +529,42 @@ int thor_hip_get_frame_key(const thor_hip_encoder* e, int stream, int i, thor_hi
   memset(out, 0, sizeof(*out));
   out->reason = log[i].key_reason;
   out->sum_intra = log[i].key_sums[0]; out->sum_best = log[i].key_sums[1]; out->n_intra = log[i].key_sums[2];
+  return 0;
+}
+// ---- temporal filter: tk_tf.h, k_tf_search / k_tf_blend ----
+static_assert(sizeof(thor_hip_tf_request) == sizeof(TfRequest), "thor_hip_tf_request and tk::TfRequest are one layout");
+int thor_hip_temporal_filter_check(const thor_hip_temporal_filter* tf) {
+  return tf && tf->size == (int)sizeof(thor_hip_temporal_filter) && tf_strength_ok(tf->strength) ? 0 : 1;
+}
+int thor_hip_filter_staged(thor_hip_encoder* e, const thor_hip_tf_request* req, int n, const thor_hip_temporal_filter* tf) {
+  if (!e || !req || n < 1 || n > 4096 || thor_hip_temporal_filter_check(tf)) return 1;
+  const TfRequest* rq = (const TfRequest*)req;
+  ENC_DISPATCH(e, {
+    auto staged = [&](int s, int i) { return i >= 0 && i < (int)E.staged[s].size() && E.staged[s][i].base_y; };
+    if (!tf_requests_ok(rq, n, e->S, staged)) return 1;
+    for (int i = 0; i < n; i++) {   // the destinations first: growing a stream's slot array moves its frames' records
+      auto& v = E.staged[rq[i].stream];
+      if ((int)v.size() <= rq[i].dst_slot) v.resize(rq[i].dst_slot + 1);
+      if (!v[rq[i].dst_slot].base_y) v[rq[i].dst_slot].alloc(e->sp.width, e->sp.height, 0);
+    }
+    std::vector<typename Engine<PIXT>::TfItem> it(n);
+    for (int i = 0; i < n; i++) {
+      auto& v = E.staged[rq[i].stream];
+      it[i].cur = &v[rq[i].slot]; it[i].dst = &v[rq[i].dst_slot]; it[i].nrefs = rq[i].nrefs;
+      for (int k = 0; k < rq[i].nrefs; k++) { it[i].ref[k] = &v[rq[i].ref_slot[k]]; it[i].dist[k] = rq[i].ref_dist[k]; }
+    }
+    E.eng.filter_frames(it.data(), n, tf->strength);
+  });
+  return 0;
+}
+int thor_hip_get_staged(thor_hip_encoder* e, int stream, int slot, void* yuv_out) {
+  if (!e || stream < 0 || stream >= e->S || slot < 0 || !yuv_out) return 1;
+  ENC_DISPATCH(e, {
+    auto& v = E.staged[stream];
+    if (slot >= (int)v.size() || !v[slot].base_y) return 1;
+    HIPCHECK(hipStreamSynchronize(g_stream));
+    download_yuv(v[slot], (PIXT*)yuv_out, e->sp.width, e->sp.height);
+  });
   return 0;
 }
 void thor_hip_kernel_time(thor_hip_encoder*, double* sb_ms, long* sb_launches, double* filter_ms) {

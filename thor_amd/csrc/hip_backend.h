@@ -423,6 +423,19 @@ template <typename PIX> void launch_rc_cost_orig(const RcJob<PIX>* jobs, const R
 }
 template void launch_rc_cost_orig<uint8_t>(const RcJob<uint8_t>*, const RcJob<uint8_t>*, int);
 template void launch_rc_cost_orig<uint16_t>(const RcJob<uint16_t>*, const RcJob<uint16_t>*, int);
+// The temporal filter of n requests of one size, on g_stream (tk_encoder.h declares it): the search of every neighbour of every request in one launch, the
+// blend of every request in the next; the stream orders them.  The caller synchronises once.
+template <typename PIX> void launch_tf(const TfJob<PIX>* jobs, const TfJob<PIX>* hjobs, int n) {
+  if (n <= 0) return;
+  const int tiles = ((hjobs[0].width + TF_TILE - 1) / TF_TILE) * ((hjobs[0].height + TF_TILE - 1) / TF_TILE);
+  int refs = 0;
+  for (int i = 0; i < n; i++) refs = hjobs[i].nrefs > refs ? hjobs[i].nrefs : refs;
+  if (refs) hipLaunchKernelGGL((k_tf_search<PIX>), dim3(tiles, refs, n), dim3(256), 0, g_stream, jobs);
+  hipLaunchKernelGGL((k_tf_blend<PIX>), dim3(tiles, n), dim3(256), 0, g_stream, jobs);
+  HIPCHECK(hipGetLastError());
+}
+template void launch_tf<uint8_t>(const TfJob<uint8_t>*, const TfJob<uint8_t>*, int);
+template void launch_tf<uint16_t>(const TfJob<uint16_t>*, const TfJob<uint16_t>*, int);
 
 // ---- helpers of the C ABI (internal linkage: the library exports nothing of them) -----------------------------------------
 namespace {

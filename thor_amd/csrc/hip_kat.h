@@ -874,6 +874,41 @@ extern "C" int thor_hip_kat_scene_cost(const void* cur, const void* prev_or_null
   else kat_scene_cost<uint16_t>((const uint16_t*)cur, (const uint16_t*)prev_or_null, w, h, out);
   return 0;
 }
+// k_tf_search + k_tf_blend on host frames, as Engine::filter_frames launches them for one request: the frames in device frames laid out like staging slots.
+template <typename PIX> static void kat_temporal_filter(const PIX* cur, const PIX* refs, const int* dists, int nrefs, int w, int h, int bitdepth, int strength, PIX* out,
+                                                        int* mv, int* wb) {
+  const size_t fsz = (size_t)w * h * 3 / 2, nb = (size_t)(w / TF_BLK) * (h / TF_BLK);
+  DevFrame<PIX> fc, fo, fr[TF_MAX_REFS];
+  fc.alloc(w, h, 0); fo.alloc(w, h, 0);
+  upload_yuv(fc, cur, w, h);
+  for (int k = 0; k < nrefs; k++) { fr[k].alloc(w, h, 0); upload_yuv(fr[k], refs + (size_t)k * fsz, w, h); }
+  DevBuf<TfBlock> blk(nb * TF_MAX_REFS);
+  DevBuf<TfJob<PIX>> dj(1);
+  TfJob<PIX> J;
+  J.cur = fc.p; J.dst = fo.p;
+  for (int k = 0; k < TF_MAX_REFS; k++) { J.ref[k] = k < nrefs ? fr[k].p : fc.p; J.dist[k] = k < nrefs ? dists[k] : 1; }
+  J.nrefs = nrefs; J.width = w; J.height = h; J.strength = strength; J.sh = bitdepth - 8; J.blk = blk.p;
+  backend::h2d(dj.p, &J, sizeof(J));
+  launch_tf<PIX>(dj.p, &J, 1);
+  backend::dev_sync();
+  download_yuv(fo, out, w, h);
+  std::vector<TfBlock> hb(nb * TF_MAX_REFS);
+  backend::d2h(hb.data(), blk.p, hb.size() * sizeof(TfBlock));
+  for (size_t i = 0; i < nb * nrefs; i++) { mv[2 * i] = hb[i].dx; mv[2 * i + 1] = hb[i].dy; wb[i] = hb[i].wb; }
+  fc.release(); fo.release();
+  for (int k = 0; k < nrefs; k++) fr[k].release();
+}
+extern "C" int thor_hip_kat_temporal_filter(const void* cur, const void* refs, const int* dists, int nrefs, int w, int h, int bitdepth, int strength, void* out, int* mv,
+                                            int* wb) {
+  if (!cur || !out || !mv || !wb || nrefs < 0 || nrefs > TF_MAX_REFS || (nrefs && (!refs || !dists)) || !tf_strength_ok(strength)) return 1;
+  if (w % 8 || h % 8 || w < 16 || h < 16 || w > 8192 || h > 8192 || (bitdepth != 8 && bitdepth != 10 && bitdepth != 12)) return 1;
+  for (int k = 0; k < nrefs; k++)
+    if (dists[k] != 1 && dists[k] != 2) return 1;
+  if (!ensure_init_any()) return 3;
+  if (bitdepth == 8) kat_temporal_filter<uint8_t>((const uint8_t*)cur, (const uint8_t*)refs, dists, nrefs, w, h, bitdepth, strength, (uint8_t*)out, mv, wb);
+  else kat_temporal_filter<uint16_t>((const uint16_t*)cur, (const uint16_t*)refs, dists, nrefs, w, h, bitdepth, strength, (uint16_t*)out, mv, wb);
+  return 0;
+}
 // k_rgb_in / k_rgb_out on host buffers, like the two above: the device copy keeps the host pointer's offset from a 16-byte boundary.
 static int kat_rgb_args(const void* rgb, const void* planar, const thor_hip_rgb_format* fmt, int w, int h, int input_bitdepth, int bitdepth, RgbFormat& R) {
   auto ok = [](int d) { return d == 8 || d == 10 || d == 12; };

@@ -324,4 +324,66 @@ template <typename PIX, bool PREV_ORIG> __global__ __launch_bounds__(256) void k
     if (v) atomicAdd(&J.out[tid], v);
   }
 }
+
+// ---- temporal filter (tk_tf.h: tf_block_search, tf_block_record, tf_blend_quad) --------
+// k_tf_search: requests along z, their neighbours along y (a workgroup beyond its request's nrefs leaves at once).  One workgroup per tile of TF_TILE x
+// TF_TILE luma samples (4 x 4 blocks): its 256 lanes load the current tile and the neighbour's tile with a halo of TF_RANGE into LDS, four samples per
+// lane and load - the window starts at a multiple of 8, so a group of four lies wholly inside or outside the plane; outside is zeros, which no legal
+// candidate reads.  Then each wavefront takes every fourth block: one lane per candidate vector (five rounds of 64 for the 289), packed SADs on dwords,
+// a DPP minimum of the (SAD, rank) keys, and lane 0 stores the block's record.  LDS: 3.3 KiB (8-bit) / 6.6 KiB (16-bit).
+template <typename PIX> __global__ __launch_bounds__(256) void k_tf_search(const TfJob<PIX>* jobs) {
+  struct alignas(4 * sizeof(PIX)) Quad { PIX v[4]; };
+  const TfJob<PIX>& J = jobs[blockIdx.z];
+  const int k = (int)blockIdx.y;
+  if (k >= J.nrefs) return;   // the same for the whole workgroup, before its barrier
+  __shared__ __attribute__((aligned(16))) PIX s_cur[TF_TILE * TF_TILE];
+  __shared__ __attribute__((aligned(16))) PIX s_ref[TF_WIN * TF_WIN + 8];   // + 8: tf_sad8x8 reads one dword beyond a row's last
+  const int tid = (int)threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int W = J.width, H = J.height;
+  const int tiles_x = (W + TF_TILE - 1) / TF_TILE;
+  const int tx0 = ((int)blockIdx.x % tiles_x) * TF_TILE, ty0 = ((int)blockIdx.x / tiles_x) * TF_TILE;
+  {
+    const int lx = (tid & 7) * 4, ly = tid >> 3, gx = tx0 + lx, gy = ty0 + ly;
+    Quad q = {{0, 0, 0, 0}};
+    if (gx < W && gy < H) __builtin_memcpy(&q, __builtin_assume_aligned(J.cur.y + (size_t)gy * J.cur.sy + gx, sizeof(Quad)), sizeof(Quad));
+    __builtin_memcpy(__builtin_assume_aligned(s_cur + ly * TF_TILE + lx, sizeof(Quad)), &q, sizeof(Quad));
+  }
+  const PIX* ry = J.ref[k].y;
+  const int rsy = J.ref[k].sy;
+  for (int i = tid; i < TF_WIN * TF_WIN / 4; i += 256) {
+    const int wx = (i % (TF_WIN / 4)) * 4, wy = i / (TF_WIN / 4);
+    const int gx = tx0 - TF_RANGE + wx, gy = ty0 - TF_RANGE + wy;
+    Quad q = {{0, 0, 0, 0}};
+    if (gx >= 0 && gx + 4 <= W && gy >= 0 && gy < H) __builtin_memcpy(&q, __builtin_assume_aligned(ry + (size_t)gy * rsy + gx, sizeof(Quad)), sizeof(Quad));
+    __builtin_memcpy(__builtin_assume_aligned(s_ref + wy * TF_WIN + wx, sizeof(Quad)), &q, sizeof(Quad));
+  }
+  if (tid < 8) s_ref[TF_WIN * TF_WIN + tid] = 0;
+  __syncthreads();
+  const int bw = W / TF_BLK, nb = bw * (H / TF_BLK);
+  for (int b = wave; b < (TF_TILE / TF_BLK) * (TF_TILE / TF_BLK); b += 4) {   // b, and with it every branch below, is the same in all lanes of a wavefront
+    const int lx = (b % (TF_TILE / TF_BLK)) * TF_BLK, ly = (b / (TF_TILE / TF_BLK)) * TF_BLK;
+    const int x0 = tx0 + lx, y0 = ty0 + ly;
+    if (x0 >= W || y0 >= H) continue;
+    const unsigned key = wave_min_u32_dpp(tf_block_search(s_cur + ly * TF_TILE + lx, TF_TILE, s_ref, (ly + TF_RANGE) * TF_WIN + lx + TF_RANGE, TF_WIN, x0, y0, W, H, lane, 64));
+    if (lane == 0) J.blk[(size_t)k * nb + (y0 / TF_BLK) * bw + x0 / TF_BLK] = tf_block_record(key, J.sh, J.strength, J.dist[k]);
+  }
+}
+// k_tf_blend: requests along y, one workgroup per tile of TF_TILE x TF_TILE luma samples and its two 16 x 16 chroma tiles.  One lane per four neighbouring
+// samples of a row: 256 lanes for the luma tile, 64 each for U and V; a group lies inside one block, reads that block's records, its own four samples
+// and the displaced four of every neighbour with a weight from the planes, and stores four samples at once.  No LDS.  nrefs 0 copies the frame.
+template <typename PIX> __global__ __launch_bounds__(256) void k_tf_blend(const TfJob<PIX>* jobs) {
+  const TfJob<PIX>& J = jobs[blockIdx.y];
+  const int tid = (int)threadIdx.x;
+  const int W = J.width, H = J.height;
+  const int tiles_x = (W + TF_TILE - 1) / TF_TILE;
+  const int tx0 = ((int)blockIdx.x % tiles_x) * TF_TILE, ty0 = ((int)blockIdx.x / tiles_x) * TF_TILE;
+  {
+    const int x = tx0 + (tid & 7) * 4, y = ty0 + (tid >> 3);
+    if (x < W && y < H) tf_blend_quad(J, 0, x, y);
+  }
+  if (tid < 128) {
+    const int l = tid & 63, x = tx0 / 2 + (l & 3) * 4, y = ty0 / 2 + (l >> 2);
+    if (x < W / 2 && y < H / 2) tf_blend_quad(J, 1 + (tid >> 6), x, y);
+  }
+}
 }  // namespace tk

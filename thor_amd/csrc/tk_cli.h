@@ -39,6 +39,10 @@ struct CliArgs {
   std::vector<int> key_frames;
   int key_scenecut = 0, key_min_interval = 0;
   bool key_given = false;    // one of the three was given: front-end options like -pixfmt
+  // -tf_strength S [-tf_past P -tf_future F]: the temporal noise filter (tk_tf.h) of every frame against its P previous and F next frames of the chunk (each 0 .. 2;
+  // frames beyond the ends of the chunk are dropped from the list) before it is coded.  S = 0 (the default) is off; P and F default to 0.
+  int tf_strength = 0, tf_past = 0, tf_future = 0;
+  bool tf_given = false;     // one of the three was given: front-end options like -pixfmt
   // Options of the reference's table (enc/strings.c:287-356) this path does not implement.  A value other than
   // the reference's default would change the bitstream, so it is recorded here and rejected by the caller
   // (thor_hip_params_set / thor_hip_params_from_config return non-zero, the CLI tools exit) - never ignored.
@@ -125,6 +129,14 @@ static inline void cli_apply(CliArgs& a, const std::vector<std::string>& t) {
       }
       else if (k == "-key_scenecut") { a.key_scenecut = I(); ok = a.key_scenecut >= 0 && a.key_scenecut <= 100; }
       else { a.key_min_interval = I(); ok = a.key_min_interval >= 0; }
+      if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
+    }
+    else if (k == "-tf_strength" || k == "-tf_past" || k == "-tf_future") {
+      a.tf_given = true;
+      bool ok = true;
+      if (k == "-tf_strength") { a.tf_strength = I(); ok = a.tf_strength == 0 || tf_strength_ok(a.tf_strength); }
+      else if (k == "-tf_past") { a.tf_past = I(); ok = a.tf_past >= 0 && a.tf_past <= 2; }
+      else { a.tf_future = I(); ok = a.tf_future >= 0 && a.tf_future <= 2; }
       if (!ok && a.unsupported.empty()) a.unsupported = k + " " + v;
     }
     else if (k == "-width") p.width = I();
@@ -290,7 +302,42 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       if (sc_resolve(a.key_scenecut, a.key_min_interval, scc) && scc.on()) eng.set_scene_cut(s, scc);
     }
   std::vector<std::vector<uint8_t>> recs((size_t)a.streams * a.num_frames);  // recon in display order
-  auto upload = [&](int s) { if (use_scale) eng.stage_scaled_host(frame.data(), eng.st[s].orig.p); else if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
+  auto upload_plain = [&](int s) { if (use_scale) eng.stage_scaled_host(frame.data(), eng.st[s].orig.p); else if (use_rgb) eng.stage_rgb_host(frame.data(), rgb, eng.st[s].orig.p); else if (use_layout) eng.stage_layout_host(frame.data(), lay, eng.st[s].orig.p); else eng.upload_orig(s, frame.data()); };
+  auto read_frame = [&](size_t idx) {
+    if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); return false; }
+    return true;
+  };
+  // The scheduled frame of stream s into its original.  -tf_strength: the frame and its neighbours of the chunk are staged in frames of their own and the filter
+  // writes the stream's original - what thorenc_hip does with staging slots beyond the chunk.
+  std::vector<DevFrame<PIX>> tfbuf;
+  auto load = [&](int s) -> bool {
+    if (a.tf_strength == 0) {
+      if (!read_frame((size_t)eng.st[s].cur_abs)) return false;
+      upload_plain(s);
+      return true;
+    }
+    if (tfbuf.empty()) {
+      tfbuf.resize(1 + TF_MAX_REFS);
+      for (auto& b : tfbuf) b.alloc(p.width, p.height, 0);
+    }
+    const int f = eng.st[s].cur.frame_num;
+    const size_t base = (size_t)eng.st[s].cur_abs - (size_t)f;
+    typename Engine<PIX>::TfItem it;
+    it.cur = &tfbuf[0]; it.dst = &eng.st[s].orig; it.nrefs = 0;
+    int nb[TF_MAX_REFS];
+    for (int d = 1; d <= a.tf_past; d++) if (f - d >= 0) { nb[it.nrefs] = f - d; it.dist[it.nrefs++] = d; }
+    for (int d = 1; d <= a.tf_future; d++) if (f + d < a.num_frames) { nb[it.nrefs] = f + d; it.dist[it.nrefs++] = d; }
+    const DevFrame<PIX> keep = eng.st[s].orig;
+    for (int k = 0; k <= it.nrefs; k++) {
+      if (!read_frame(base + (size_t)(k ? nb[k - 1] : f))) return false;
+      eng.st[s].orig = tfbuf[k];
+      upload_plain(s);
+      if (k) it.ref[k - 1] = &tfbuf[k];
+    }
+    eng.st[s].orig = keep;
+    eng.filter_frames(&it, 1, a.tf_strength);
+    return true;
+  };
   auto download = [&](int s) { if (use_rgb) eng.fetch_rgb_host(eng.st[s].rec.p, rec.data(), rgb); else if (use_layout) eng.fetch_layout_host(eng.st[s].rec.p, rec.data(), lay); else eng.download_rec(s, rec.data()); };
   // THOR_STAGGER=1 (tests): the streams in two groups half a frame apart (Engine::encode_run) instead of lock step
   if (getenv("THOR_STAGGER") && atoi(getenv("THOR_STAGGER")) && a.streams > 1) {
@@ -298,9 +345,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
     eng.encode_run(a.num_frames,
         [&](int s) -> bool {
           if (!eng.schedule(s)) return false;
-          const size_t idx = (size_t)eng.st[s].cur_abs;
-          if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) { fprintf(stderr, "short read at frame %zu\n", idx); rc = 3; return false; }
-          upload(s);
+          if (!load(s)) { rc = 3; return false; }
           return true;
         },
         [&](int first, int count) {
@@ -315,12 +360,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
     for (int s = 0; s < a.streams; s++) {
       if (!eng.schedule(s)) continue;
       active++;
-      size_t idx = (size_t)eng.st[s].cur_abs;
-      if (fseek(fi, (long)(idx * fsz), SEEK_SET) || fread(frame.data(), 1, fsz, fi) != fsz) {
-        fprintf(stderr, "short read at frame %zu\n", idx);
-        return 3;
-      }
-      upload(s);
+      if (!load(s)) return 3;
       fp[s] = eng.st[s].cur;
     }
     if (!active) break;
@@ -386,6 +426,7 @@ template <typename PIX> int cli_run(const CliArgs& a) {
       append_stat_file(a.statfile.c_str(), format_stat_line(eng.st[s].log, eng.st[s].sh_bits, p.frame_rate, p.width, p.height, p.input_bitdepth, a.num_frames));
   }
   fflush(stdout);
+  for (auto& b : tfbuf) b.release();
   eng.close();
   fclose(fi);
   return 0;

@@ -21,6 +21,7 @@
 #include "tk_filters.h"
 #include "tk_scale.h"
 #include "tk_rc.h"
+#include "tk_tf.h"
 #include "tk_report.h"
 
 namespace tk {
@@ -85,6 +86,8 @@ template <typename PIX> void launch_scale_in(const void* frame, const PixLayout&
 template <typename PIX> void launch_rc_cost(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n);
 // The same against previous originals (RcJob::prev_y): the kernel's other instantiation, which stores nothing but the sums.
 template <typename PIX> void launch_rc_cost_orig(const RcJob<PIX>* jobs, const RcJob<PIX>* hjobs, int n);
+// The temporal filter (tk_tf.h) of n requests: k_tf_search for every neighbour of every request, then k_tf_blend, two launches on the library's stream.
+template <typename PIX> void launch_tf(const TfJob<PIX>* jobs, const TfJob<PIX>* hjobs, int n);
 #endif
 
 // ---- parameters -------------------------------------------------------------------------
@@ -488,6 +491,9 @@ template <typename PIX> class Engine {
   unsigned long long* d_rcsums = nullptr;
   RcJob<PIX>* d_scjob = nullptr;          // scene_cost: its one job and its sums (allocated on first use)
   unsigned long long* d_scsums = nullptr;
+  TfJob<PIX>* d_tfjobs = nullptr;         // filter_frames: its jobs and the block records of tf_cap requests (allocated on first use, grown on demand)
+  TfBlock* d_tfblk = nullptr;
+  int tf_cap = 0;
 
   // Frames cross the engine's boundary at the INPUT depth (upload_orig, download_rec, the files of cli_run): one byte per sample for depth 8, two otherwise.
   int depth_shift() const { return sp.bitdepth - sp.input_bitdepth; }
@@ -607,6 +613,8 @@ template <typename PIX> class Engine {
     backend::dev_free(d_rcsums); d_rcsums = nullptr;
     backend::dev_free(d_scjob); d_scjob = nullptr;
     backend::dev_free(d_scsums); d_scsums = nullptr;
+    backend::dev_free(d_tfjobs); d_tfjobs = nullptr;
+    backend::dev_free(d_tfblk); d_tfblk = nullptr; tf_cap = 0;
   }
 
   // A packed frame of input-depth samples in device memory -> planes at the engine's depth (v << shift), and back (rounded and saturated).  Only with
@@ -862,6 +870,41 @@ template <typename PIX> class Engine {
 #endif
     backend::dev_sync();
     backend::d2h(sums, d_scsums, 3 * sizeof(unsigned long long));
+  }
+  // The temporal filter (tk_tf.h) of n requests in one launch sequence with one synchronisation: every `cur` against its neighbours into its `dst`, which
+  // is none of the call's sources - the caller checks (tf_requests_ok).  Originals in, a pure function of them out; nothing of a stream's state is touched.
+  struct TfItem {
+    const DevFrame<PIX>* cur; const DevFrame<PIX>* dst;
+    const DevFrame<PIX>* ref[TF_MAX_REFS];
+    int dist[TF_MAX_REFS], nrefs;
+  };
+  // Per-block vectors and weights of the last filter_frames call, request i: TF_MAX_REFS * (width / 8) * (height / 8) records (the known-answer entry reads them).
+  size_t tf_blocks_per_request() const { return (size_t)TF_MAX_REFS * (sp.width / TF_BLK) * (sp.height / TF_BLK); }
+  void filter_frames(const TfItem* it, int n, int strength) {
+    if (n > tf_cap) {
+      backend::dev_free(d_tfjobs); backend::dev_free(d_tfblk);
+      d_tfjobs = (TfJob<PIX>*)backend::dev_alloc((size_t)n * sizeof(TfJob<PIX>));
+      d_tfblk = (TfBlock*)backend::dev_alloc((size_t)n * tf_blocks_per_request() * sizeof(TfBlock));
+      tf_cap = n;
+    }
+    std::vector<TfJob<PIX>> hj(n);
+    for (int i = 0; i < n; i++) {
+      TfJob<PIX>& J = hj[i];
+      J.cur = it[i].cur->p; J.dst = it[i].dst->p;
+      for (int k = 0; k < TF_MAX_REFS; k++) {
+        J.ref[k] = k < it[i].nrefs ? it[i].ref[k]->p : it[i].cur->p;
+        J.dist[k] = k < it[i].nrefs ? it[i].dist[k] : 1;
+      }
+      J.nrefs = it[i].nrefs; J.width = sp.width; J.height = sp.height; J.strength = strength; J.sh = sp.bitdepth - 8;
+      J.blk = d_tfblk + (size_t)i * tf_blocks_per_request();
+    }
+#if TK_HOST
+    for (int i = 0; i < n; i++) tf_filter_frame(hj[i]);
+#else
+    backend::h2d(d_tfjobs, hj.data(), (size_t)n * sizeof(TfJob<PIX>));
+    launch_tf<PIX>(d_tfjobs, hj.data(), n);
+#endif
+    backend::dev_sync();
   }
   // Rate control of stream s from its next frame on (tk_rc.h; c.on() false: off).  Legal while the stream's log is empty: before its first frame or right
   // after begin_sequence - the caller checks.  The controller starts empty and the next analysis has no previous frame.

@@ -6,6 +6,7 @@
  *               [-src_width W -src_height H] [-scale_filter bilinear|bicubic] [-scale_site left|centre]
  *               [-rc_bitrate N] [-rc_buffer_ms M] [-rc_min_qp Q -rc_max_qp Q] [-rc_min_qpI Q -rc_max_qpI Q] [-rc_initial_qp Q]
  *               [-key_frames a,b,c] [-key_scenecut PCT] [-key_min_interval N]
+ *               [-tf_strength S] [-tf_past P] [-tf_future F]
  * -pixfmt: the layout of the -if and -rf files, rows tight (default i420: planar).  nv12 / nv21 interleave the chroma samples; p010 does so with
  * the samples in the high bits of 16-bit words and serves any input depth above 8.  The frames are staged and fetched in that layout
  * (thor_hip_stage_frame_layout / thor_hip_get_recon_layout): the device converts.
@@ -18,6 +19,10 @@
  * the fields of thor_hip_rate_control.  They are not the reference's -bitrate / -max_qp ..., which stay refused.
  * -key_frames a,b,c: key frames at these frames of every stream's chunk (thor_hip_force_key_frame); -key_scenecut PCT [-key_min_interval N]: scene cuts
  * (thor_hip_set_scene_cut; no default, 0 is off).  Low-delay configurations only.
+ * -tf_strength S (1 .. 16; 0, the default, is off): the temporal noise filter (thor_hip_filter_staged) of every frame against its -tf_past P previous and
+ * -tf_future F next frames of the stream's chunk (each 0 .. 2, default 0; frames beyond the ends of the chunk are dropped from the list).  The originals are
+ * staged in slots beyond the chunk and filtered into the slots the encoder reads, all streams of a frame in one call.  The report's PSNR is then measured
+ * against the filtered frames: they are what is coded.
  * With -streams S > 1, stream s encodes frames [skip + s*N, skip + (s+1)*N) as its own closed
  * stream and writes <of>.<s> / <rf>.<s> (the reference's -skip/-n chunking).
  * stdout: the reference's report (enc/mainenc.c:219-226, :553-591, :642-650; PSNR measured on the GPU unless -snrcalc 0) - with
@@ -65,6 +70,8 @@ int main(int argc, char** argv) {
   thor_hip_scene_cut sc = {sizeof(thor_hip_scene_cut), 0, 0};
   const char* key_frames = NULL;
   int key_given = 0;
+  thor_hip_temporal_filter tf = {sizeof(thor_hip_temporal_filter), 0};
+  int tf_past = 0, tf_future = 0;
   int n = 600, skip = 0, S = 1, i, wrap = 0, snrcalc = 1;
   thor_hip_params_from_config(&p, NULL);
   /* config files first, explicit options afterwards (same precedence as the reference) */
@@ -99,6 +106,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(k, "-key_frames")) { key_frames = v; key_given = 1; }
     else if (!strcmp(k, "-key_scenecut")) { sc.percent = atoi(v); key_given = 1; }
     else if (!strcmp(k, "-key_min_interval")) { sc.min_interval = atoi(v); key_given = 1; }
+    else if (!strcmp(k, "-tf_strength")) tf.strength = atoi(v);
+    else if (!strcmp(k, "-tf_past")) tf_past = atoi(v);
+    else if (!strcmp(k, "-tf_future")) tf_future = atoi(v);
     else if (!strcmp(k, "-wrap")) wrap = atoi(v); /* clip length: frame index taken modulo this (throughput tests) */
     else if (!strcmp(k, "-log2_sb_size") ? thor_hip_params_set_sb_size(&p, atoi(v)) : thor_hip_params_set(&p, k, v)) { fprintf(stderr, "Run-time error...\noption %s %s is unknown or not implemented by this path\n...now exiting to system...\n", k, v); return 2; }
   }
@@ -133,19 +143,37 @@ int main(int argc, char** argv) {
   if (thor_hip_rate_control_check(&rc)) { fprintf(stderr, "Run-time error...\nthe -rc_ options do not describe a rate control (a negative value, a minimum above its maximum, a QP above 51)\n...now exiting to system...\n"); return 2; }
   if (key_given && p.num_reorder_pics != 0) { fprintf(stderr, "Run-time error...\nthe -key_ options need a low-delay configuration (num_reorder_pics 0)\n...now exiting to system...\n"); return 2; }
   if (thor_hip_scene_cut_check(&sc) || (key_frames && key_frames[strspn(key_frames, "0123456789,")])) { fprintf(stderr, "Run-time error...\nthe -key_ options do not describe key frames (-key_scenecut 0 .. 100, -key_min_interval >= 0, -key_frames a,b,c)\n...now exiting to system...\n"); return 2; }
+  if ((tf.strength && thor_hip_temporal_filter_check(&tf)) || tf_past < 0 || tf_past > 2 || tf_future < 0 || tf_future > 2) { fprintf(stderr, "Run-time error...\nthe -tf_ options do not describe a temporal filter (-tf_strength 0 .. 16, -tf_past and -tf_future 0 .. 2)\n...now exiting to system...\n"); return 2; }
   thor_hip_encoder* e = thor_hip_open(&p, S, 0);
   if (!e) { fprintf(stderr, "thor_hip_open failed\n"); return 3; }
   size_t fsz = rgb ? thor_hip_rgb_bytes(e, rgb) : thor_hip_frame_bytes(e); /* -if and -rf hold samples of the INPUT bit depth, or RGB frames */
   size_t isz = scaled ? thor_hip_scale_bytes(e, &scale, lay) : fsz;        /* -if at the source size */
   unsigned char* frame = (unsigned char*)malloc(isz);
   thor_hip_set_frame_distortion(e, snrcalc != 0);
+  const int tfo = tf.strength ? n : 0; /* with the filter the originals go to slots n .. 2n - 1 and the filtered frames to the slots the encoder reads */
   for (int s = 0; s < S; s++)
     for (int f = 0; f < n; f++) {
       size_t idx = (size_t)skip + (size_t)s * n + f;
       if (wrap > 0) idx %= (size_t)wrap;
       if (fseek(fi, (long)(idx * isz), SEEK_SET) || fread(frame, 1, isz, fi) != isz) { fprintf(stderr, "short read at frame %zu\n", idx); return 4; }
-      if (scaled ? thor_hip_stage_frame_scaled(e, s, f, frame, &scale, lay, 0) : rgb ? thor_hip_stage_frame_rgb(e, s, f, frame, rgb, 0) : lay ? thor_hip_stage_frame_layout(e, s, f, frame, lay, 0) : thor_hip_stage_frame(e, s, f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
+      if (scaled ? thor_hip_stage_frame_scaled(e, s, tfo + f, frame, &scale, lay, 0) : rgb ? thor_hip_stage_frame_rgb(e, s, tfo + f, frame, rgb, 0) : lay ? thor_hip_stage_frame_layout(e, s, tfo + f, frame, lay, 0) : thor_hip_stage_frame(e, s, tfo + f, frame)) { fprintf(stderr, "staging failed\n"); return 4; }
     }
+  double ttf = 0;
+  if (tf.strength) { /* one call per frame: the requests of all streams */
+    thor_hip_tf_request* req = (thor_hip_tf_request*)calloc(S, sizeof(thor_hip_tf_request));
+    double a = now_s();
+    for (int f = 0; f < n; f++) {
+      for (int s = 0; s < S; s++) {
+        thor_hip_tf_request* r = &req[s];
+        r->stream = s; r->dst_slot = f; r->slot = tfo + f; r->nrefs = 0;
+        for (int d = 1; d <= tf_past; d++) if (f - d >= 0) { r->ref_slot[r->nrefs] = tfo + f - d; r->ref_dist[r->nrefs++] = d; }
+        for (int d = 1; d <= tf_future; d++) if (f + d < n) { r->ref_slot[r->nrefs] = tfo + f + d; r->ref_dist[r->nrefs++] = d; }
+      }
+      if (thor_hip_filter_staged(e, req, S, &tf)) { fprintf(stderr, "temporal filter refused\n"); return 4; }
+    }
+    ttf = now_s() - a;
+    free(req);
+  }
   FILE** fr = (FILE**)calloc(S, sizeof(FILE*));
   char name[4096];
   for (int s = 0; s < S && rf; s++) {
@@ -235,6 +263,7 @@ int main(int argc, char** argv) {
   double sb_ms = 0, filt_ms = 0; long launches = 0;
   thor_hip_kernel_time(e, &sb_ms, &launches, &filt_ms);
   double mpx = (double)p.width * p.height * n * S / 1e6;
+  if (tf.strength) fprintf(stdout, "thorenc_hip: temporal filter strength %d, %d past / %d future: %.3f s for %d call(s)\n", tf.strength, tf_past, tf_future, ttf, n);
   fprintf(stdout, "thorenc_hip: %d stream(s) x %d frame(s) %dx%d: encode %.3f s (%.3f Mpx/s), total %.3f s; superblock kernels %.1f ms in %ld launches, filters %.1f ms\n",
           S, n, p.width, p.height, tenc, mpx / tenc, now_s() - t0, sb_ms, launches, filt_ms);
   if (getenv("THOR_PROF")) {
